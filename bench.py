@@ -3,7 +3,7 @@
 100-batch activation matching + LAP (71 groups) + partial merge + 400-step PLeaS (401 Adam updates) --
 on synthetic 224x224 inputs, on N MI355X GPUs of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--arch resnet101] [--batch 16]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--arch resnet101] [--batch 16] [--dump-outputs DIR]
 
 A STEP is ONE WHOLE JOB (100 matching batches + 71 LAPs + merge + 401 updates on one set of synthetic batches that is
 resident in HBM).  ``--steps K`` times exactly K jobs back to back, bracketed by barrier + synchronize on both sides
@@ -44,6 +44,7 @@ sys.path.insert(0, ROOT)
 
 FP32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md, chip-level parameters
 FULL_MATCH, FULL_PLEAS = 100, 401
+DUMP_BYTES = 60 * 10 ** 6  # array data of --dump-outputs: with the .npy headers the files stay inside 64 MB
 T_START = time.time()
 
 
@@ -120,6 +121,10 @@ def parse(argv=None):
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="profiling aid, single process: time rank 0's share of an N-rank job with the collectives "
                          "skipped (PLEAS_EMULATE_WORLD); the line is tagged emulated and is NOT a benchmark result")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed jobs, write what the last one returned (merged model, permutations, costs, "
+                         "per-layer losses) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; an array too "
+                         "large for its share is written as a fixed seeded sample of its elements (dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -199,19 +204,21 @@ class Pool:
 
 
 def build_models(arch, device, batch):
+    """The seeded pair, BatchNorm calibrated ON THE HOST: on the device the vendor's convolutions pick their kernels from a
+    database that earlier processes write, so the calibrated statistics -- the job's inputs -- could change run to run."""
     from pleas_merging_amd import resnet as zoo
 
     models = []
     gen = torch.Generator(device=device)
     for seed in (0, 1):
         torch.manual_seed(seed)
-        m = zoo.MODELS[arch](num_classes=1000).to(device)
+        m = zoo.MODELS[arch](num_classes=1000)
         calib = []
         for i in range(4):
             gen.manual_seed(900 + i)
-            calib.append(torch.randn(batch, 3, 224, 224, generator=gen, device=device))
+            calib.append(torch.randn(batch, 3, 224, 224, generator=gen, device=device).cpu())
         zoo.calibrate_bn(m, calib)
-        models.append(m)
+        models.append(m.to(device))
     return models
 
 
@@ -343,6 +350,41 @@ def check_result(spec, res, full=True):
     if full:   # a handful of updates of a shortened debug job need not bring every layer's loss down
         out["ok"] = bool(out["ok"] and out["loss_last_update"] < out["loss_first_update"] and fell >= 0.9 * (first.numel() - 1))
     return out
+
+
+def dump_outputs(res, spec, out_dir):
+    """--dump-outputs: what the job handed its caller -- the merged model's state dict, every group's permutation and cost
+    matrix, the per-layer losses of the first and last update -- as ``out_dir/<name>.npy``; integer and fp64 tensors as
+    float64, the others as float32.  DUMP_BYTES is shared out smallest array first: an array within its share is written
+    whole, a larger one as a 1-D sample of its flat elements at sorted indices drawn by a generator seeded with the CRC-32
+    of its name, so every run and every build of the project writes the same elements.  Returns (files, bytes)."""
+    import zlib
+
+    import numpy as np
+
+    arrays = {"merged." + k: v for k, v in res["m3"].state_dict().items()}
+    for k in spec:
+        key = str(k).replace(":", ".")
+        arrays["perm." + key] = res["perm"][k]
+        arrays["costs." + key] = res["costs"][k]
+    for name in ("first_loss", "last_loss"):
+        if res[name] is not None:      # the closed form has no per-update losses
+            arrays[name] = res[name]
+    wide = {n: t.dtype == torch.float64 or not t.dtype.is_floating_point for n, t in arrays.items()}
+    itemsize = {n: 8 if wide[n] else 4 for n in arrays}
+    order = sorted(arrays, key=lambda n: (arrays[n].numel() * itemsize[n], n))
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES
+    for i, name in enumerate(order):
+        t = arrays[name].detach()
+        n = min(t.numel(), left // (len(order) - i) // itemsize[name])
+        if n < t.numel():
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), n, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if wide[name] else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    return len(order), DUMP_BYTES - left
 
 
 def time_normal_eq(spec, m1, m2, perm, costs, loader, ratio, sources_per_forward=None):
@@ -1006,6 +1048,9 @@ def main():
             all(torch.equal(prev_res["costs"][k], res["costs"][k]) and torch.equal(prev_res["perm"][k], res["perm"][k]) for k in spec)
             and all(torch.equal(v, sd_b[k]) for k, v in sd_a.items()))
     prev_res = None
+    if rank == 0 and args.dump_outputs:      # before any extra job can touch the result
+        files, nbytes = dump_outputs(res, spec, args.dump_outputs)
+        log("outputs of the last timed job: %d arrays, %.1f MB -> %s" % (files, nbytes / 1e6, args.dump_outputs))
 
     # ---- untimed extras (every rank takes part in the phases job: it contains collectives)
     phases = None

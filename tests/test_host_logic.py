@@ -291,7 +291,9 @@ def test_host_code_under_sanitizers():
     lib = build.build_sanitized()
     syms = subprocess.check_output(["nm", "-D", lib], text=True)
     assert "__asan_report" in syms and "__ubsan_handle" in syms          # the host code really is instrumented
-    env = dict(os.environ, LD_PRELOAD=build.asan_runtime(), ASAN_OPTIONS="detect_leaks=0:halt_on_error=1",
+    # the runtime goes first (ASan insists) and whatever the environment already preloads stays
+    preload = " ".join(p for p in (build.asan_runtime(), os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     out = subprocess.run([sys.executable, os.path.join(REPO, "tests", "sanitize_driver.py"), lib], env=env,
                          capture_output=True, text=True, timeout=600)
