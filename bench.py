@@ -3,13 +3,17 @@
 100-batch activation matching + LAP (71 groups) + partial merge + 400-step PLeaS (401 Adam updates) --
 on synthetic 224x224 inputs, on N MI355X GPUs of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--arch resnet101] [--batch 16] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--arch resnet101] [--batch 16] [--dump-outputs DIR] [--full]
 
 A STEP is ONE WHOLE JOB (100 matching batches + 71 LAPs + merge + 401 updates on one set of synthetic batches that is
 resident in HBM).  ``--steps K`` times exactly K jobs back to back, bracketed by barrier + synchronize on both sides
 (max over ranks); ``value`` = that time / K = seconds per job = BASELINE.json's metric; ``ms_per_step`` = 1000 * value.
 ``--warmup W`` runs W untimed jobs first.  ``--match-batches`` / ``--updates`` shorten the job for debugging only (the
 line then says SHORTENED and is not a benchmark result).
+
+A plain run does only what the headline needs: set-up, W + K jobs, the dump (``--dump-outputs``), the line.  ``--full``
+adds the untimed legs marked (full) below, each on jobs or samples of its own after the timed region; the ``--no-*``
+options switch single legs off in such a run.
 
 N > 1: the driver starts one rank per GPU with ``python -m torch.distributed.run ... bench.py --gpus N``; when started
 WITHOUT that launcher (``python bench.py --gpus N``) this script starts it itself, before anything touches the GPU, and
@@ -20,15 +24,19 @@ arena, so every rank applies the identical update.
 Besides the contract's keys the JSON line carries
   roofline      the own kernel with the most time in the timed jobs: algorithmic flop per launch / HIP-event time of
                 its launches inside the timed region, against the 157.3 TFLOP/s fp32 matrix peak (+ roofline_other);
-  cpu_baseline  the CPU oracle (restatement of the reference) on this box's host cores, on the job's own first batches
+  cpu_baseline  (full) the CPU oracle (restatement of the reference) on the host's cores, on the job's own first batches
                 at the job's batch size (bounded count), N = 1 only; the same sample gives checks.parity_vs_oracle;
-  phases_s      one more (untimed, synchronised) job split into spec / matching / LAP / merge + set-up / updates;
-  alt_solver    the closed-form PLeaS phase (solver="normal_eq": MFMA normal equations + batched Cholesky), N = 1;
-  library_baseline  the reference's loops with STOCK PyTorch-ROCm operators on the same GPU (torch.cdist, autograd convolutions,
-                torch.optim.Adam, scipy LAP after D2H), bounded sample scaled like cpu_baseline, N = 1 only;
-  vendor        the frozen source forwards of the PLeaS phase (own convolutions since round 5 + pleas_bn_act) timed alone;
-  checks        invariants of the last timed job's result (permutations valid, losses fell, weights finite) and
-                parity_vs_oracle: the HIP job with the timed knobs against the oracle on the same batches (exit 3 on failure).
+  phases_s      (full) one more (untimed, synchronised) job split into spec / matching / LAP / merge + set-up / updates;
+  inputs        (full) the other input mode (host / resident batches) on jobs of its own, N = 1;
+  alt_solver    (full) the closed-form PLeaS phase (solver="normal_eq": MFMA normal equations + batched Cholesky), N = 1;
+  alt_arith     (full) the same job under the split-bf16 arithmetic, N = 1;
+  library_baseline  (full) the reference's loops with STOCK PyTorch-ROCm operators on the same GPU (torch.cdist, autograd
+                convolutions, torch.optim.Adam, scipy LAP after D2H), bounded sample scaled like cpu_baseline, N = 1 only;
+  vendor, bn_reset  (full) the frozen source forwards of the PLeaS phase (own convolutions since round 5 + pleas_bn_act)
+                timed alone; the BatchNorm reset of the merged model, N = 1;
+  checks        invariants of the last timed job's result (permutations valid, losses fell, weights finite; exit 3 on
+                failure) and, in a full run, parity_vs_oracle: the HIP job with the timed knobs against the oracle on the
+                same batches.
 """
 import argparse
 import gc
@@ -72,6 +80,10 @@ def parse(argv=None):
                          "batches b %% N == rank, ONE all-reduce of the A / B arenas, layer-sharded batched Cholesky, ONE sum of "
                          "the solved parameter arena) -- the path whose exchange does not grow with the updates; the line is "
                          "tagged ALT-SOLVER and is not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed jobs, also run the untimed legs (phases, other input mode, closed form, BN reset, "
+                         "sources alone, split-bf16 arithmetic, stock-operator and CPU baselines, parity with the oracle); "
+                         "off: only set-up, warm-up, timed jobs, --dump-outputs and the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt-solver", action="store_true", help="skip the closed-form (normal equations) leg")
     ap.add_argument("--no-library-baseline", action="store_true", help="skip the stock-PyTorch-ROCm-operators leg on the GPU")
@@ -971,7 +983,7 @@ def main():
         dist.barrier()
 
     n_match, n_pleas = max(1, args.match_batches), max(1, args.updates)
-    full = (n_match, n_pleas) == (FULL_MATCH, FULL_PLEAS)
+    full_size = (n_match, n_pleas) == (FULL_MATCH, FULL_PLEAS)
     n_sched = max(1, n_pleas - 1)  # CosineAnnealingLR(T_max=MAX_STEPS) with MAX_STEPS + 1 updates
     m1, m2 = build_models(args.arch, device, args.batch)
     log("models built + BN calibrated")
@@ -979,7 +991,9 @@ def main():
     spec = get_permutation_spec(m1, ((1, 3, 224, 224),))
     spec_s = time.perf_counter() - t0
     ranks = max(world, args.emulate_world)
-    pool = Pool(max(n_match, n_pleas), args.batch, device, host=(world == 1 and args.emulate_world <= 1) or args.inputs == "host")
+    # pinned host copies: for timed jobs that take their batches from the host, or for the other input mode's leg (full)
+    pool = Pool(max(n_match, n_pleas), args.batch, device,
+                host=(args.full and world == 1 and args.emulate_world <= 1) or args.inputs == "host")
     pool.where = args.inputs
     dp = world > 1
     if args.emulate_world > 1:
@@ -1039,7 +1053,7 @@ def main():
     value = elapsed / max(1, args.steps)
     prof = hip_ops.profile_collect() if rank == 0 else {}  # the timed jobs' kernels, before anything else is timed
     fwd_lanes = hip_ops.fwd_plan_lanes() if rank == 0 else None   # forms of the grouped forward: measured ms, lane
-    checks = check_result(spec, res, full) if rank == 0 else None
+    checks = check_result(spec, res, full_size) if rank == 0 else None
     if rank == 0 and prev_res is not None and world == 1 and args.emulate_world <= 1:
         # the same job on the same batches twice in a row inside the timed region: the same bits?  (costs, assignments, every
         # tensor of the merged model; tests/test_hip_determinism.py holds the library to it)
@@ -1052,14 +1066,14 @@ def main():
         files, nbytes = dump_outputs(res, spec, args.dump_outputs)
         log("outputs of the last timed job: %d arrays, %.1f MB -> %s" % (files, nbytes / 1e6, args.dump_outputs))
 
-    # ---- untimed extras (every rank takes part in the phases job: it contains collectives)
+    # ---- untimed extras, --full only (every rank takes part in the phases job: it contains collectives)
     phases = None
-    if not args.no_phases:
+    if args.full and not args.no_phases:
         ph = Phases(on=True, verbose=args.phase_log)
         job(ph)
         phases = dict(ph.out)
     alt = vendor = bn_reset = inputs_cmp = None
-    if world == 1 and args.emulate_world <= 1 and pool.host_items:
+    if args.full and world == 1 and args.emulate_world <= 1 and pool.host_items:
         # the other input mode on extra jobs (one untimed first: its allocator pools / pinned staging are new)
         other = "host" if args.inputs == "resident" else "resident"
         pool.where = other
@@ -1081,7 +1095,7 @@ def main():
                               "activation_matching.py:121, pleas_merging.py:266)"}
         log("inputs from %s: %s s per job (timed jobs, from %s: %.3f)" % (other, inputs_cmp[other + "_s_per_job"], args.inputs, value))
     alt_emulated = None
-    if world == 1 and args.emulate_world > 1 and not args.no_alt_solver:
+    if args.full and world == 1 and args.emulate_world > 1 and not args.no_alt_solver:
         # rank 0's share of the CLOSED FORM under data parallelism: whole batches b % W == 0 are accumulated, ONE exchange of
         # the A / B arenas at the end (skipped here), every rank solves every layer
         mine = pool.loader(0, n_pleas)[::args.emulate_world]
@@ -1090,7 +1104,7 @@ def main():
         alt_emulated["note"] = ("rank 0's share (%d of %d batches) of solver='normal_eq' in a %d-rank job; the all-reduce of the "
                                 "A / B arenas before the solve is NOT included" % (len(mine), n_pleas, args.emulate_world))
         log("closed form, emulated rank of %d: accumulate %.2fs, solve %.2fs" % (args.emulate_world, a["accumulate_s"], a["solve_s"]))
-    if world == 1 and args.emulate_world <= 1:
+    if args.full and world == 1 and args.emulate_world <= 1:
         if not args.no_alt_solver and args.solver == "adam":
             alt = time_normal_eq(spec, m1, m2, res["perm"], res["costs"], pool.loader(0, n_pleas), args.ratio,
                                  cfg["sources_per_forward"])
@@ -1104,10 +1118,10 @@ def main():
                           "both models, %d samples per forward) with nothing else on the GPU; the key keeps its rounds 1-4 name; "
                           "rocprofv3 kernel shares: profiles/" % ((cfg["sources_per_forward"] or 2) * args.batch)}
     alt_arith = None
-    if world == 1 and args.emulate_world <= 1 and not args.no_alt_arith and args.solver == "adam":
+    if args.full and world == 1 and args.emulate_world <= 1 and not args.no_alt_arith and args.solver == "adam":
         alt_arith = time_alt_arith(job, res, spec, value, n_match, world, rank, args)
     library = None
-    if world == 1 and args.emulate_world <= 1 and not args.no_library_baseline and args.solver == "adam":
+    if args.full and world == 1 and args.emulate_world <= 1 and not args.no_library_baseline and args.solver == "adam":
         library = library_baseline(cfg, spec, m1, m2, pool, n_match, n_pleas, n_sched, args.cpu_match_batches, args.cpu_updates,
                                    res["perm"], res["costs"])
         library["own_kernels_speedup"] = round(library["value"] / value, 2)
@@ -1186,7 +1200,7 @@ def main():
                 "workload": "%s pair (random init, BN calibrated), ONE JOB per step: %d matching batches + LAP (%d groups) + "
                             "partial merge (ratio %.2f) + %d PLeaS Adam updates, batch %d x 3x224x224%s"
                             % (args.arch, n_match, len(spec), args.ratio, n_pleas, args.batch,
-                               "" if full else " (SHORTENED job: not a benchmark result)"),
+                               "" if full_size else " (SHORTENED job: not a benchmark result)"),
                 "solver": args.solver, "parallelism": "dp%d" % world,
                 "sources_per_forward": cfg["sources_per_forward"] or 2 * ranks,
                 "matching_batches_per_forward": cfg["match_per_forward"] or 2,
@@ -1201,6 +1215,7 @@ def main():
                                             "vendor": "MIOpen / Tensile for every convolution of the frozen source / twin forwards "
                                                       "(rounds 1-4; not run-to-run deterministic)"}[source_conv_mode()],
                 "not_in_value": "get_permutation_spec %.2f s (host, once per model)" % spec_s,
+                "untimed_legs": "run (--full)" if args.full else "not run (plain run: --full adds them)",
             },
             "job_s": {"mean": round(value, 4), "median": round(srt[len(srt) // 2], 4), "min": round(srt[0], 4),
                       "max": round(srt[-1], 4), "note": "rank 0's per-job times; value = bracketed total / steps"},
@@ -1221,7 +1236,7 @@ def main():
                                % (args.emulate_world, "replaced by a %.0f us stall of the update stream" % args.emulate_allreduce_us
                                   if args.emulate_allreduce_us > 0 else "skipped"))
             out["metric"] = "EMULATED " + out["metric"]
-        if world == 1 and not args.no_cpu_baseline and args.emulate_world <= 1 and args.solver == "adam":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.emulate_world <= 1 and args.solver == "adam":
             out["cpu_baseline"], parity, parity_alt = cpu_baseline_and_parity(cfg, spec, m1, m2, pool, n_match, n_pleas, n_sched,
                                                                               args.cpu_match_batches, args.cpu_updates,
                                                                               alt_arith=alt_arith is not None)

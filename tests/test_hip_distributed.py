@@ -177,8 +177,38 @@ def test_two_rank_normal_eq_equals_single_process(tiny_bottleneck):
         assert (v == results[1][2][k]).all(), k      # both ranks hold the same model
 
 
+def test_bench_plain_run_line(tmp_path):
+    """`python bench.py --gpus 1` without --full: set-up, warm-up, the timed job, the dump and the line -- the contract's keys,
+    the roofline of the timed job's own events and its checks, and none of the legs that run jobs or samples of their own."""
+    import json
+    import subprocess
+
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--arch", "resnet18",
+           "--batch", "4", "--match-batches", "3", "--updates", "9", "--prefetch-groups", "1", "--prefetch-memory", "0.05",
+           "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 1 and line["warmup"] == 1 and line["unit"] == "s"
+    assert line["higher_is_better"] is False and line["dtype"] == "f32" and line["metric"].startswith("wall-clock")
+    assert line["value"] > 0 and abs(line["ms_per_step"] - 1e3 * line["value"]) < 1.0
+    assert line["checks"]["ok"] and line["roofline"]["launches"] > 0
+    assert line["config"]["untimed_legs"].startswith("not run")
+    for key in ("phases_s", "inputs", "alt_solver", "alt_arith", "library_baseline", "vendor", "bn_reset", "cpu_baseline"):
+        assert key not in line, key
+    assert "parity_vs_oracle" not in line["checks"]
+    assert (dump / "first_loss.npy").exists() and (dump / "last_loss.npy").exists()
+    assert any(p.name.startswith("merged.") for p in dump.iterdir())
+
+
 def test_bench_self_launches_two_ranks():
-    """`python bench.py --gpus 2` WITHOUT a launcher (the way the driver starts --gpus 1): the script starts
+    """`python bench.py --gpus 2 --full` WITHOUT a launcher (the way the driver starts --gpus 1): the script starts
     torch.distributed.run itself before touching the GPU, both ranks run the whole data-parallel job (gloo here: RCCL
     refuses two ranks on one device), rank 0 prints ONE valid JSON line and the parent exits with the ranks' status."""
     import json
@@ -189,7 +219,7 @@ def test_bench_self_launches_two_ranks():
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--all-ranks-on-gpu0",
            "--steps", "1", "--warmup", "1", "--arch", "resnet18", "--batch", "4", "--match-batches", "3", "--updates", "9",
-           "--prefetch-groups", "1", "--prefetch-memory", "0.05", "--no-cpu-baseline"]
+           "--prefetch-groups", "1", "--prefetch-memory", "0.05", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -728,6 +728,14 @@ def test_bench_starts_its_own_ranks_without_touching_the_gpu(monkeypatch):
     assert (d.gpus, d.steps, d.warmup, d.match_batches, d.updates) == (1, 3, 1, 100, 401)
 
 
+def test_bench_untimed_legs_only_with_full():
+    """A plain bench run does only what its headline needs; the untimed legs are asked for with --full."""
+    import importlib
+
+    bench = importlib.import_module("bench")
+    assert not bench.parse([]).full and bench.parse(["--full"]).full
+
+
 def test_drop_in_namespace_exports_the_reference_surface():
     """Every name the reference's package __init__ files export (pleas/methods/__init__.py:12-41,
     pleas/core/__init__.py:9-21) resolves under the drop-in ``pleas`` namespace, so driver imports keep working."""

@@ -3,7 +3,7 @@
 # PROJECTION material, not a multi-GPU measurement.
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O; cd $R
 for W in 2 4 8; do
-  timeout -k 10 400 python bench.py --emulate-world $W --steps 2 --warmup 1 --no-cpu-baseline > $O/r04_emulated_rank_w$W.json 2> $O/r04_emulated_rank_w$W.err || { echo "W=$W failed"; tail -5 $O/r04_emulated_rank_w$W.err; exit 1; }
+  timeout -k 10 400 python bench.py --emulate-world $W --steps 2 --warmup 1 --full --no-cpu-baseline > $O/r04_emulated_rank_w$W.json 2> $O/r04_emulated_rank_w$W.err || { echo "W=$W failed"; tail -5 $O/r04_emulated_rank_w$W.err; exit 1; }
   python - <<PY
 import json
 d = json.loads(open("gpurun_out/r04_emulated_rank_w$W.json").read().strip().splitlines()[-1])

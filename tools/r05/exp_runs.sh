@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 while [ $# -ge 3 ]; do
   tag=$1; envs=$2; flags=$3; shift 3
   [ "$envs" = "-" ] && envs="PLEAS_EXP_TAG=$tag"
-  env $envs python bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-library-baseline --no-alt-solver $flags \
+  env $envs python bench.py --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline --no-library-baseline --no-alt-solver $flags \
       > gpurun_out/r05_exp_${name}_$tag.json 2> gpurun_out/r05_exp_${name}_$tag.err || { echo "$tag FAILED" >> $out; tail -5 gpurun_out/r05_exp_${name}_$tag.err; exit 1; }
   python - "$name" "$tag" "$envs $flags" >> $out <<'PY'
 import json, sys

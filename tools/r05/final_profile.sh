@@ -15,7 +15,7 @@ json.dump({p: hashlib.sha256(open(p, "rb").read()).hexdigest() for p in sorted(g
           open("gpurun_out/r05_${V}_source_sha.json", "w"), indent=1)
 PY
 if [ "$2" != "skip-bench" ]; then
-  timeout -k 10 700 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_${V}_bench.json 2> $O/r05_${V}_bench.err
+  timeout -k 10 700 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r05_${V}_bench.json 2> $O/r05_${V}_bench.err
   echo "bench rc $?"; grep "timed region" $O/r05_${V}_bench.err
   cd /tmp && export TMPDIR=/tmp
   rm -rf /tmp/prof_$V
