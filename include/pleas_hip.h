@@ -119,6 +119,36 @@ int pleas_lsap_batched(const float* const* cost, const int* n, int nprob, int ma
 int pleas_lsap_host(const void* cost, int is_double, int n, int maximize, int64_t* col_ind);
 
 /* ------------------------------------------------------------------------------------
+ * Batched lexicographic bottleneck assignment (square, dense), the GPU form of
+ * scipy_solve_minimax_assignment (reference pleas/core/solvers.py:88-115).
+ *
+ * Contract, for an n x n fp32 matrix A, 1 <= n <= PLEAS_LSAP_MAX_N, finite entries, maximize = 1:
+ *   1. t* = max over permutations p of min_i A[i, p(i)], comparing fp32 values (-0 == +0);
+ *   2. among the permutations that reach t*, the one with the largest sum, scipy's LAP tie rule for the rest.
+ *      Exactly: with M, m the largest and smallest entries, L = t* - (n (M - m) + max(1, |t*|)) in fp64, L32 = L
+ *      rounded toward -inf to fp32 (the call is refused if L32 is not finite), A_hat = A with every entry < t*
+ *      replaced by L32, the result is linear_sum_assignment(A_hat, maximize=True).
+ * maximize = 0 is the same call on -A (minimise the largest entry, then the sum).
+ *
+ * cost[p], n[p], col_ind[p]: as for pleas_lsap_batched (DEVICE matrices / outputs, HOST pointer arrays).
+ * t_out: DEVICE float[nprob] or NULL; receives min_i A[i, col_ind[i]] (maximize = 1) or max_i A[i, col_ind[i]]
+ *   (maximize = 0), a zero always as +0.
+ * ws: DEVICE workspace of at least pleas_bottleneck_ws_bytes(n, nprob) bytes.  It begins with int32 status[nprob],
+ *   written by the kernels: 0 ok, 1 a NaN or +-inf entry, 2 an iteration cap was hit, 3 L32 not finite.  A problem
+ *   whose status is not 0 gets col_ind = -1 everywhere and t_out = NaN.  Everything is enqueued on `stream` with no
+ *   host synchronisation, so these errors are seen by reading status once the stream has reached them.
+ * pleas_bottleneck_ws_bytes returns 0 for invalid sizes.
+ */
+size_t pleas_bottleneck_ws_bytes(const int* n, int nprob);
+int pleas_bottleneck_batched(const float* const* cost, const int* n, int nprob, int maximize, int64_t* const* col_ind,
+                             float* t_out, void* ws, size_t ws_bytes, void* stream);
+/* The same contract for ONE problem in HOST memory (fp32 when is_double == 0, else fp64: entries are then compared in
+ * fp64; L32 is rounded to fp32 all the same), synchronous, no GPU involved; returns the same col_ind as the device path.
+ * t_out (HOST, nullable) as above.  PLEAS_EINVAL for a NULL pointer, n out of [1, PLEAS_LSAP_MAX_N], a non-finite
+ * entry or a non-finite L32. */
+int pleas_bottleneck_host(const void* cost, int is_double, int n, int maximize, int64_t* col_ind, double* t_out);
+
+/* ------------------------------------------------------------------------------------
  * Block gather / average used by partial merging and by the PLeaS regression targets.
  *
  * Replaces: pleas/methods/partial_matching.py:122-129 (1-axis tensors) and :157-172

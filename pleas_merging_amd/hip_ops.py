@@ -315,6 +315,80 @@ def host_solve_lsa(A: torch.Tensor, maximize: bool = True) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------------------------------------- bottleneck assignment
+_BN_STATUS = {1: "a NaN or +-inf entry", 2: "an iteration cap was hit", 3: "the replacement value L32 is not finite"}
+
+
+def check_bottleneck_status(status: torch.Tensor) -> None:
+    """Raise ``PleasHipError`` if a status word of ``pleas_bottleneck_batched`` is not 0 (reads it: synchronises)."""
+    bad = [(i, int(s)) for i, s in enumerate(status.cpu().tolist()) if s]
+    if bad:
+        raise PleasHipError("pleas_bottleneck_batched refused problem(s) %s" %
+                            ", ".join("%d (%s)" % (i, _BN_STATUS.get(s, "status %d" % s)) for i, s in bad))
+
+
+def solve_bottleneck_batched(costs: Sequence[torch.Tensor], maximize: bool = True, t_out: Optional[torch.Tensor] = None,
+                             deferred: Optional[list] = None) -> List[torch.Tensor]:
+    """Lexicographic bottleneck assignment of every matrix in ONE batched call (include/pleas_hip.h): per matrix the
+    permutation that maximises its smallest matched entry, then the sum.  Returns device int64 vectors.  ``t_out``: an
+    optional fp32 device tensor ``[len(costs)]`` that receives the bottleneck values.  The kernels' status words are
+    read (one synchronisation) before returning, unless ``deferred`` is a list: then the status tensor is appended to
+    it, for :func:`check_bottleneck_status` once the caller reads the results anyway."""
+    if not costs:
+        return []
+    _need_gpu(*costs)
+    mats = []
+    for c in costs:
+        if c.dim() != 2 or c.shape[0] != c.shape[1] or c.shape[0] < 1:
+            raise PleasHipError("square cost matrices expected, got %s" % (tuple(c.shape),))
+        if c.shape[0] > _lib.LSAP_MAX_N:
+            raise PleasHipError("n = %d exceeds PLEAS_LSAP_MAX_N = %d" % (c.shape[0], _lib.LSAP_MAX_N))
+        mats.append(c.contiguous())
+    k = len(mats)
+    if t_out is not None and (not t_out.is_cuda or t_out.dtype != torch.float32 or t_out.numel() != k
+                              or not t_out.is_contiguous()):
+        raise PleasHipError("t_out must be a contiguous fp32 device tensor of %d elements" % k)
+    outs = [torch.empty(m.shape[0], dtype=torch.int64, device=m.device) for m in mats]
+    cost_ptrs = (ctypes.c_void_p * k)(*[m.data_ptr() for m in mats])
+    out_ptrs = (ctypes.c_void_p * k)(*[o.data_ptr() for o in outs])
+    ns = (ctypes.c_int * k)(*[m.shape[0] for m in mats])
+    lib = _lib.lib()
+    nbytes = lib.pleas_bottleneck_ws_bytes(ns, k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=mats[0].device)        # caching allocator, current stream
+    rc = lib.pleas_bottleneck_batched(cost_ptrs, ns, k, int(bool(maximize)), out_ptrs,
+                                      t_out.data_ptr() if t_out is not None else None, ws.data_ptr(), nbytes, _stream())
+    check(rc, "pleas_bottleneck_batched")
+    status = ws[:4 * k].view(torch.int32)
+    if deferred is None:
+        check_bottleneck_status(status)
+    else:
+        deferred.append(status)
+    return outs
+
+
+def hip_solve_minimax_assignment(A: torch.Tensor, maximize: bool = True) -> torch.Tensor:
+    """HIP drop-in for the reference's ``scipy_solve_minimax_assignment`` (pleas/core/solvers.py:88-115): int64
+    ``col_ind`` on ``A``'s device (the reference's tie rule differs: see INTEGRATION.md)."""
+    return solve_bottleneck_batched([A], maximize)[0]
+
+
+def host_solve_minimax_assignment(A: torch.Tensor, maximize: bool = True) -> torch.Tensor:
+    """``pleas_bottleneck_host``: the same contract on a HOST matrix (fp32 / fp64 CPU tensor), synchronous, same
+    ``col_ind`` as the device path.  Device tensors are refused."""
+    if A.is_cuda:
+        raise PleasHipError("host_solve_minimax_assignment takes a CPU tensor; use hip_solve_minimax_assignment for "
+                            "device tensors")
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
+        raise PleasHipError("square cost matrix expected, got %s" % (tuple(A.shape),))
+    if A.dtype not in (torch.float32, torch.float64):
+        A = A.double()
+    A = A.contiguous()
+    out = torch.empty(A.shape[0], dtype=torch.int64)
+    check(_lib.lib().pleas_bottleneck_host(A.data_ptr(), int(A.dtype == torch.float64), A.shape[0], int(bool(maximize)),
+                                           out.data_ptr(), None), "pleas_bottleneck_host")
+    return out
+
+
 # ---------------------------------------------------------------------------------------- bn + add + relu
 def bn_act(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor] = None,
            relu: bool = True) -> torch.Tensor:

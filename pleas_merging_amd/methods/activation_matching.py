@@ -24,7 +24,7 @@ import torch
 import torch.fx
 from torch import nn
 
-from ..core.solvers import hip_solve_lsa
+from ..core.solvers import hip_solve_lsa, hip_solve_minimax_assignment
 from ..core.utils import Axis, Permutation, PermutationSpec
 from .. import hip_ops
 from ..hip_ops import cross_features_cdist, cross_features_inner_product  # noqa: F401  (public plug-ins)
@@ -621,24 +621,34 @@ def accumulate_costs_fused(spec: PermutationSpec, model1: nn.Module, model2: nn.
 def solve_all(costs: Dict[Axis, torch.Tensor], lsa_solver: Callable, while_solving: Optional[Callable] = None) -> Permutation:
     """One LAP per group.  The default solver runs all groups in ONE batched kernel launch; ``while_solving()`` (if given)
     is called after that launch is enqueued and before its results are awaited -- the largest group keeps two CUs busy
-    for ~0.25 s, time the host can spend on work that does not need the permutation."""
-    if lsa_solver is hip_solve_lsa:
+    for ~0.25 s, time the host can spend on work that does not need the permutation.  ``hip_solve_minimax_assignment``
+    takes the same road with one batched bottleneck call."""
+    if lsa_solver is hip_solve_lsa or lsa_solver is hip_solve_minimax_assignment:
         from .. import hip_ops
 
+        pending: list = []
+        if lsa_solver is hip_solve_lsa:
+            batched = hip_ops.solve_lsa_batched
+        else:
+            def batched(mats, maximize):
+                return hip_ops.solve_bottleneck_batched(mats, maximize, deferred=pending)
         mats = list(costs.values())
         dev = mats[0].device if mats else None
         if dev is None or dev.type != "cuda" or while_solving is None:
-            outs = hip_ops.solve_lsa_batched(mats, maximize=True)
+            outs = batched(mats, maximize=True)
         else:
             # the kernel gets a stream of its own: what `while_solving` enqueues elsewhere (source forwards on side
             # streams) then runs beside it also when the caller is on torch's default stream
             caller, solver = torch.cuda.current_stream(dev), hip_ops.role_stream(dev, "lap")
             solver.wait_stream(caller)
             with torch.cuda.stream(solver):
-                outs = hip_ops.solve_lsa_batched(mats, maximize=True)
+                outs = batched(mats, maximize=True)
             while_solving()
             caller.wait_stream(solver)
-        return {k: o.cpu() for k, o in zip(costs.keys(), outs)}
+        perm = {k: o.cpu() for k, o in zip(costs.keys(), outs)}
+        for status in pending:
+            hip_ops.check_bottleneck_status(status)
+        return perm
     if while_solving is not None:
         while_solving()
     return {k: lsa_solver(v) for k, v in costs.items()}

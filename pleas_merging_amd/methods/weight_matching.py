@@ -27,7 +27,7 @@ from typing import Callable, Dict, List, Sequence, Tuple, Union
 
 import torch
 
-from ..core.solvers import hip_solve_lsa
+from ..core.solvers import hip_solve_lsa, hip_solve_minimax_assignment
 from ..core.utils import Axis, Permutation, PermutationSpec, StateDict, apply_perm, make_identity_perm
 from ..hip_ops import cross_features_inner_product
 
@@ -47,11 +47,16 @@ class _Visitor:
         self.device = next(iter(state_as[0].values())).device
         # on the device: default callables = the grouped launch + the batched LAP kernel
         self.grouped = cross_weights is cross_features_inner_product
-        self.device_lap = lsa_solver is hip_solve_lsa
+        self.device_lap = lsa_solver is hip_solve_lsa or lsa_solver is hip_solve_minimax_assignment
         if self.grouped or self.device_lap:
             from .. import hip_ops
 
             self.ops = hip_ops
+            if lsa_solver is hip_solve_minimax_assignment:
+                # status words read before the gathers below use the indices (one small read per batch)
+                self.batched_lap = lambda mats: hip_ops.solve_bottleneck_batched(mats, maximize=True)
+            else:
+                self.batched_lap = lambda mats: hip_ops.solve_lsa_batched(mats, maximize=True)
             if self.device.type != "cuda":
                 raise hip_ops.PleasHipError(
                     "weight_matching: state dicts are on %s; the default HIP cross_weights / lsa_solver need GPU tensors "
@@ -117,10 +122,10 @@ class _Visitor:
         """One batch of mutually independent visits: ``[(A, new, report)]`` per group, in order."""
         if self.grouped and self.device_lap:
             mats = self._score_grouped(ps)
-            news = self.ops.solve_lsa_batched(mats, maximize=True)
+            news = self.batched_lap(mats)
         else:
             mats = [self._score_grouped((p,))[0] if self.grouped else self._score(p) for p in ps]
-            news = [self.ops.solve_lsa_batched([A], maximize=True)[0] if self.device_lap else self.lsa_solver(A) for A in mats]
+            news = [self.batched_lap([A])[0] if self.device_lap else self.lsa_solver(A) for A in mats]
         out = []
         for p, A, new in zip(ps, mats, news):
             pick = new.to(A.device)
