@@ -372,6 +372,14 @@ int pleas_loss_final(const float* partials, const int* n_partials, const float* 
 size_t pleas_wgrad_batch_ws_bytes(const pleas_wgrad_layer* layers, int n_layers);
 int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, void* ws, size_t ws_bytes, int ws_fresh,
                       void* stream);
+/* Host only (no GPU): what the plan builder of pleas_wgrad_batch decides for `layers` under the current pleas_arith, six ints
+ * per layer: [0] the tile form `variant` (bit 0: 64-row tiles, bit 1: 64-column tiles, bit 2: scalar loads of the residual,
+ * bit 3: shifted one-pixel loader of the input, bit 4: shifted through aligned 16-byte loads, bit 5: "virtual channels" --
+ * rows are (channel, tap) pairs, layers with fewer than 16 input channels --, bit 6: split-bf16 kernel), [1] S, the slabs of
+ * the pixel axis (> 1: slabs + reduce), [2] / [3] output-channel / input-channel tiles, [4] work items, [5] 1 when the
+ * epilogue stages the tile through LDS and writes 16-byte rows (the pointers may be NULL: a 16-byte aligned gradient and
+ * workspace are assumed then).  Returns 0 or a negative error code. */
+int pleas_wgrad_plan_info(const pleas_wgrad_layer* layers, int n_layers, int* info);
 
 /* ------------------------------------------------------------------------------------
  * The path's exchange step under data parallelism (no reference counterpart -- the reference is

@@ -81,6 +81,7 @@ SIGNATURES = {
     "pleas_conv2d_bn_act_fwd": (c_int, [c_void_p] * 8 + [c_int] * 11 + [c_void_p]),
     "pleas_wgrad_batch_ws_bytes": (c_size_t, [c_void_p, c_int]),
     "pleas_wgrad_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "pleas_wgrad_plan_info": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "pleas_gram_batch_ws_bytes": (c_size_t, [c_void_p, c_int, POINTER(c_int), c_int]),
     "pleas_gram_batch": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int), c_int, c_int, c_int, c_void_p,
                                  c_size_t, c_int, c_void_p]),

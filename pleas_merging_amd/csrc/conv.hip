@@ -56,6 +56,11 @@ struct WgradItemDev {
     int layer, tm, tn, r, split, c_begin, c_end, pad;
 };
 
+// Does the epilogue of a layer's tiles stage its accumulators through LDS and write 16-byte runs along ci (`rows` in
+// wgrad_tile)?  `dst` is what the tiles write to: the layer's slabs when S > 1, else its gradient.  One expression for the
+// kernel and for the host query pleas_wgrad_plan_info (a macro: the kernel's code is the expression it always was).
+#define PLEAS_WGRAD_ROWS_PATH(S, kpos, R, Cin, dst) (((S) > 1 || (kpos) || (R) == 1) && ((Cin) & 3) == 0 && (((size_t)(dst)) & 15) == 0)
+
 // YMODE: 0 = Y read in place (1x1, stride 1), 1 = shifted / strided view, one pixel per load, 2 = stride-1 "same" layer
 // with HW % 4 == 0: tap r reads the SAME flat pixel run `delta = dh * W + dw` further on, so a thread's four pixels are
 // ONE 16-byte load at a 4-byte-aligned address (the hardware takes it; two aligned loads + a register shift move twice the
@@ -357,7 +362,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
     // loop's last barrier) and every thread writes 16-byte runs along ci; otherwise one element per lane as before.
     const int R = L.KH * L.KW;
     const bool kpos = (L.flags & PLEAS_WGRAD_KPOS_MAJOR) != 0;
-    const bool rows = (L.S > 1 || kpos || R == 1) && (L.Cin & 3) == 0 && (((size_t)(L.S > 1 ? L.slab : L.out)) & 15) == 0;
+    const bool rows = PLEAS_WGRAD_ROWS_PATH(L.S, kpos, R, L.Cin, L.S > 1 ? L.slab : L.out);
     if (rows) {
         // SPLIT tiles of 128 rows stage one 64-row half at a time (the waves of row half h): the staging tile then fits the
         // split images' 52 KB and three workgroups share a CU
@@ -820,6 +825,31 @@ extern "C" size_t pleas_wgrad_batch_ws_bytes(const pleas_wgrad_layer* layers, in
     WgradPlan tmp;
     if (build_wgrad_plan(tmp, layers, n_layers) != PLEAS_OK) return 0;
     return tmp.total;
+}
+
+extern "C" int pleas_wgrad_plan_info(const pleas_wgrad_layer* layers, int n_layers, int* info) {
+    if (!layers || n_layers <= 0 || !info) return bad_arg("wgrad_plan_info: empty layer list / null output");
+    WgradPlan tmp;
+    const int rc = build_wgrad_plan(tmp, layers, n_layers);
+    if (rc != PLEAS_OK) return rc;
+    for (int i = 0; i < 6 * n_layers; ++i) info[i] = 0;
+    for (const WgradItemDev& it : tmp.items)
+        if (it.layer >= 0) {
+            int* o = info + 6 * it.layer;
+            o[2] = std::max(o[2], it.tm + 1);
+            o[3] = std::max(o[3], it.tn + 1);
+            ++o[4];
+        }
+    for (int i = 0; i < n_layers; ++i) {
+        const WgradLayerDev& d = tmp.layers[i];
+        int* o = info + 6 * i;
+        o[0] = d.variant;
+        o[1] = d.S;
+        // the tiles' destination as the launch sees it: slabs at their offset in a 16-byte aligned workspace, else the gradient
+        const size_t dst = d.S > 1 ? tmp.off_slabs + reinterpret_cast<size_t>(d.slab) * sizeof(float) : (size_t)(uintptr_t)layers[i].grad;
+        o[5] = PLEAS_WGRAD_ROWS_PATH(d.S, (d.flags & PLEAS_WGRAD_KPOS_MAJOR) != 0, d.KH * d.KW, d.Cin, dst) ? 1 : 0;
+    }
+    return PLEAS_OK;
 }
 
 extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, void* ws, size_t ws_bytes, int ws_fresh,

@@ -952,6 +952,24 @@ class WgradBatch:
 
         return None if self._arr is None else np.frombuffer(self._arr, dtype=np.dtype(type(self._arr[0])))
 
+    @staticmethod
+    def plan_info(geometries) -> List[dict]:
+        """Host-side facts about the grouped launch of a layer list (``pleas_wgrad_plan_info``; no GPU work, no tensors):
+        per ``(N, Cout, Cin, Hin, Win, KH, KW, stride, pad, flags)`` the tile form ``variant`` the plan builder picks under the
+        current ``pleas_arith``, the slabs ``S`` of the pixel axis, the tile counts, the work items, and whether the epilogue
+        takes the staged 16-byte row path (for 16-byte aligned destinations)."""
+        geometries = list(geometries)
+        n = len(geometries)
+        if n == 0:
+            return []
+        arr = (_lib.WgradLayer * n)()
+        for a, geo in zip(arr, geometries):
+            a.N, a.Cout, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad, a.flags = (int(v) for v in geo)
+        info = (ctypes.c_int * (6 * n))()
+        check(_lib.lib().pleas_wgrad_plan_info(arr, n, info), "pleas_wgrad_plan_info")
+        return [{"variant": info[6 * i], "S": info[6 * i + 1], "tiles_cout": info[6 * i + 2], "tiles_cin": info[6 * i + 3],
+                 "items": info[6 * i + 4], "rows": bool(info[6 * i + 5])} for i in range(n)]
+
     def relaunch(self) -> None:
         """The launch of the latest ``flush`` again, with the table as it is now."""
         if self._keep or self._arr is None or self._ws is None:

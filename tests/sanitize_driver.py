@@ -78,6 +78,9 @@ def main():
             # normal-equation launch takes layers with >= 16 input channels
             expect(lib.pleas_wgrad_batch_ws_bytes(wg, n) > 0, "wgrad plan with the stem " + arch)
             expect(lib.pleas_wgrad_batch_ws_bytes(ctypes.byref(wg, ctypes.sizeof(_lib.WgradLayer)), n - 1) > 0, "wgrad plan " + arch)
+            winfo = (ctypes.c_int * (6 * n))()
+            expect(lib.pleas_wgrad_plan_info(wg, n, winfo) == 0 and all(winfo[6 * i + 1] >= 1 and winfo[6 * i + 4] >= 1 for i in range(n))
+                   and (winfo[0] & 32) != 0, "wgrad plan info (the stem on virtual channels) " + arch)
             expect(lib.pleas_normal_eq_ws_bytes(ctypes.byref(neq, ctypes.sizeof(_lib.NeqLayer)), n - 1) > 0, "neq plan " + arch)
             expect(lib.pleas_normal_eq_plan_info(ctypes.byref(neq, ctypes.sizeof(_lib.NeqLayer)), n - 1, info) == 0 and info[1] > 0,
                    "neq plan info " + arch)
@@ -112,6 +115,11 @@ def main():
         expect(lib.pleas_normal_eq_plan_info(bad, 1, info) == 0 and info[3] > 0, "lag classes of %r" % (geo,))
     expect(lib.pleas_normal_eq_finalize(None, 0, None) == -22, "finalize(NULL)")
     expect(lib.pleas_fwd_batch_ws_bytes(None, 0) == 0 and lib.pleas_wgrad_batch_ws_bytes(None, 3) == 0, "NULL layer lists")
+    badw = (_lib.WgradLayer * 1)()
+    badw[0].N, badw[0].Cout, badw[0].Cin, badw[0].Hin, badw[0].Win, badw[0].KH, badw[0].KW, badw[0].stride, badw[0].pad = 4, 64, 64, 2, 2, 7, 7, 1, 0
+    one = (ctypes.c_int * 6)()
+    expect(lib.pleas_wgrad_plan_info(badw, 1, one) == -22 and lib.pleas_wgrad_plan_info(None, 3, one) == -22 and
+           lib.pleas_wgrad_plan_info(badw, 1, None) == -22, "wgrad plan info must refuse an empty output / NULL")
     # ---- compute entry points with arguments their validation refuses (nothing is launched)
     expect(lib.pleas_gram_accum(None, None, 1, 4, 4, 0, 0, None, None, 0, None) == -22, "gram_accum(NULL)")
     n1 = (ctypes.c_int * 1)(4097)

@@ -19,18 +19,7 @@ import test_hip_fullsize_dp as dp
 pytestmark = pytest.mark.gpu
 
 
-GEOMETRIES = [
-    # (N, Cin, H, W, Cout, k, stride, pad, bias)
-    (4, 64, 56, 56, 64, 3, 1, 1, False),       # flat-shift k x k form, kernel-position-major weights
-    (3, 128, 28, 28, 96, 3, 1, 1, True),       # Cout not a multiple of the tile, bias
-    (2, 128, 56, 56, 128, 3, 2, 1, False),     # strided 3 x 3: general form
-    (2, 3, 224, 224, 64, 7, 2, 3, False),      # the stem: K = 147, scalar weight loads
-    (5, 512, 7, 7, 512, 3, 1, 1, False),       # 7 x 7 images (HW % 4 != 0)
-    (2, 32, 17, 23, 40, 5, 1, 2, True),        # H != W, 5 x 5
-    (2, 48, 15, 15, 24, 3, 1, 0, False),       # "valid" padding, Cin % 32 != 0
-    (3, 256, 14, 14, 1024, 1, 1, 0, False),    # 1 x 1 (mode "all")
-    (2, 256, 56, 56, 512, 1, 2, 0, False),     # strided 1 x 1 (mode "all")
-]
+from tile_cases import GEOMETRIES, GEOMETRIES_BN_EXTRA  # noqa: E402  (shared with the coverage ledger, tests/test_tile_coverage.py)
 
 
 @pytest.mark.parametrize("geo", GEOMETRIES)
@@ -56,8 +45,7 @@ def test_conv2d_vs_fp64_and_repeatable(geo):
 
 
 @pytest.mark.parametrize("arith", ["fp32", "split_bf16"])
-@pytest.mark.parametrize("geo", GEOMETRIES + [(2, 64, 56, 56, 256, 1, 1, 0, False),      # short-K 1 x 1, 128-row tiles
-                                              (3, 2048, 7, 7, 512, 1, 1, 0, False)])     # 1 x 1 on 7 x 7 images
+@pytest.mark.parametrize("geo", GEOMETRIES + GEOMETRIES_BN_EXTRA)
 def test_conv2d_bn_act_equals_the_two_launches_it_replaces(geo, arith):
     """``pleas_conv2d_bn_act_fwd``: the convolution's output AND its BatchNorm / add / ReLU image from one launch -- both
     ``torch.equal`` to ``conv2d`` followed by ``bn_act`` (with and without identity, with and without ReLU), every tile form,

@@ -625,30 +625,7 @@ def test_gram_batch_deterministic_and_overwrite(ops):
 
 
 # ------------------------------------------------------------------------------------------ PLeaS layer kernels
-WGRAD_CASES = [
-    # N, Cout, Cin, H, W, k, stride, pad
-    (4, 256, 64, 14, 14, 1, 1, 0),     # 1x1: direct loader, TN = 64
-    (4, 64, 256, 14, 14, 1, 1, 0),     # TM = 64
-    (3, 96, 80, 7, 7, 1, 1, 0),        # HW = 49: scalar loads, ragged tiles
-    (4, 128, 128, 14, 14, 3, 1, 1),    # 3x3 shifted loader, padding
-    (2, 40, 24, 9, 11, 3, 1, 1),       # ragged everything, non-square image
-    (4, 128, 64, 28, 28, 3, 2, 1),     # 3x3 stride 2
-    (4, 256, 128, 28, 28, 1, 2, 0),    # 1x1 stride 2 (downsample)
-    (2, 64, 64, 56, 56, 3, 1, 1),      # long pixel axis -> split into slabs + reduce
-    (16, 64, 32, 1, 1, 1, 1, 0),       # linear-like (HW = 1)
-    # fewer than 16 input channels: rows of the tile are (channel, tap) pairs ("virtual channels")
-    (4, 64, 3, 224, 224, 7, 2, 3),     # the ResNet stem (K = 147, slabs + reduce)
-    (2, 8, 3, 9, 11, 3, 1, 1),         # tiny, ragged, one tile
-    (2, 20, 5, 12, 12, 5, 2, 2),       # 5x5 stride 2: 125 virtual channels, HWo = 36
-    (3, 70, 15, 7, 7, 3, 1, 1),        # 135 virtual channels: TN = 128, HW = 49 (scalar residual loads)
-    # images with HW % 4 != 0 on stride-1 same-size layers (one pixel per load; a padded-pixel 16-byte form was built and measured
-    # in round 5: no gain on these short-K layers, profiles/r05_padk_ab.txt -- the cases stay)
-    (4, 96, 64, 7, 7, 3, 1, 1),        # 3x3 at 7 x 7 (layer4)
-    (16, 512, 512, 7, 7, 3, 1, 1),     # the same at ResNet size: 128 x 128 tiles, 25 chunks
-    (16, 2048, 512, 7, 7, 1, 1, 0),    # 1x1 at 7 x 7, batch 16 (layer4 conv3)
-    (2, 20, 32, 5, 5, 5, 1, 2),        # 5x5 "same" on a 5 x 5 image (HW = 25)
-    (1, 33, 17, 3, 3, 1, 1, 0),        # one sample, HW = 9: the last row's run is clamped at the tensor's end
-]
+from tile_cases import FWD_CASES, WGRAD_CASES  # noqa: E402  (shared with the coverage ledger, tests/test_tile_coverage.py)
 
 
 @pytest.mark.parametrize("N,Cout,Cin,H,W,k,stride,pad", WGRAD_CASES)
@@ -801,30 +778,6 @@ def test_cholesky_solve_ridge_and_breakdown_flag(ops):
 
 
 # ------------------------------------------------------------------------------------------ fused forward + target + residual + loss
-FWD_CASES = [
-    # N, Cout, Cin, H, W, k, stride, pad, bias
-    (4, 256, 64, 14, 14, 1, 1, 0, False),
-    (4, 64, 256, 14, 14, 1, 1, 0, False),     # TM = 64
-    (3, 96, 80, 7, 7, 1, 1, 0, False),        # ragged pixels / channels
-    (4, 128, 128, 14, 14, 3, 1, 1, False),    # 3x3 with padding
-    (2, 40, 24, 9, 11, 3, 1, 1, False),       # non-square image
-    (4, 128, 64, 28, 28, 3, 2, 1, False),     # stride 2
-    (3, 72, 96, 10, 7, 3, 1, 1, False),       # kernel-position-major with ragged rows / pixels, non-square image
-    (2, 64, 32, 12, 12, 5, 1, 2, False),      # 5x5 taps
-    (2, 64, 3, 32, 32, 7, 2, 3, False),       # stem geometry: Kd = 147 (scalar weight loads)
-    (16, 70, 300, 1, 1, 1, 1, 0, True),       # linear layer with bias
-    # flat-shift tile forms (stride 1, "same" padding, Cin % 32 == 0): one LDS image per channel block, taps = shifts
-    (5, 200, 96, 14, 14, 1, 1, 0, False),     # 1x1, 16-B pixel loads, ragged last pixel tile (980 pixels) and channel tile
-    (3, 136, 64, 7, 7, 1, 1, 0, False),       # 1x1, HW = 49: scalar pixel loads, tiles straddle samples
-    (16, 40, 64, 1, 1, 1, 1, 0, True),        # linear layer on the flat path (HW = 1), TM = 64, bias
-    (5, 136, 64, 14, 14, 3, 1, 1, False),     # 3x3: tiles straddle samples and rows, every border case
-    (2, 64, 32, 56, 56, 3, 1, 1, False),      # 3x3 at W = 56: widest halo (242 data columns), TM = 64
-    (3, 130, 96, 7, 7, 3, 1, 1, False),       # 3x3 at 7x7: halo 8, three samples per tile
-    (2, 72, 32, 9, 11, 5, 1, 2, False),       # 5x5 "same", non-square image
-    (3, 96, 64, 28, 28, 3, 1, 1, True),       # 3x3 at W = 28 with bias
-]
-
-
 @pytest.mark.parametrize("N,Cout,Cin,H,W,k,stride,pad,bias", FWD_CASES)
 def test_fwd_batch_matches_conv_and_target(ops, N, Cout, Cin, H, W, k, stride, pad, bias):
     import torch.nn.functional as F
