@@ -38,6 +38,8 @@ inline int bad_arg(const char* what) {
     } while (0)
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// every table of a plan starts on a 256-byte boundary of the caller's workspace
+inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // Pointers that reach a kernel through a device-side table are "generic" to hipcc, which then emits
 // flat_load / flat_store: those count on lgkmcnt as well as vmcnt, so every LDS wait in the MFMA loop
@@ -148,6 +150,36 @@ struct PlanCache {
     void claims_workspace(const Plan& p) {
         for (auto& o : slots)
             if (&o != &p && (int)o.key.size() > WS && (int)p.key.size() > WS && o.key[WS] == p.key[WS]) o.uploaded = false;
+    }
+};
+
+// ---- N side streams of the library + the events to fork from / join into the caller's stream, one set per device (streams
+// belong to the device that was current when they were created), created on first use and kept for the process; no device
+// memory.  Every grouped launch that forks owns an instance, so two launches never wait on each other's events.  Guarded by
+// the caller's mutex.
+template <int N>
+struct SideStreams {
+    struct Set {
+        hipStream_t streams[N];
+        hipEvent_t forked, joined[N];
+        bool ok = false;        // false: creation failed, everything goes back to back on the caller's stream
+    };
+    static constexpr int kMaxDev = 16;
+    Set sets[kMaxDev], none;
+    bool tried[kMaxDev] = {false};
+    Set& current() {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return none;
+        Set& s = sets[dev];
+        if (!tried[dev]) {
+            tried[dev] = true;
+            bool ok = hipEventCreateWithFlags(&s.forked, hipEventDisableTiming) == hipSuccess;
+            for (int i = 0; ok && i < N; ++i)
+                ok = hipStreamCreateWithFlags(&s.streams[i], hipStreamNonBlocking) == hipSuccess &&
+                     hipEventCreateWithFlags(&s.joined[i], hipEventDisableTiming) == hipSuccess;
+            s.ok = ok;
+        }
+        return s;
     }
 };
 

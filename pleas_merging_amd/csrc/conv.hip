@@ -454,29 +454,11 @@ __device__ __forceinline__ void wgrad_dispatch(const WgradLayerDev& L, const Wgr
     else wgrad_tile<TM, TN, 1, 1>(L, it, smem);
 }
 
-#ifndef PLEAS_WGRAD_TIMELINE
-#define PLEAS_WGRAD_TIMELINE 0   // study builds (tools/r04/timeline.sh): per work item, when and where it ran
-#endif
-#if PLEAS_WGRAD_TIMELINE
-__device__ long long g_wgrad_timeline[16384][4];   // start, end (100 MHz wall clock), HW_ID | XCC_ID << 32, chunks * TM * TN
-#endif
-
 __global__ __launch_bounds__(cThreads, 2) void wgrad_batch_kernel(const WgradLayerDev* __restrict__ layers,
                                                                const WgradItemDev* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const WgradItemDev it = items[blockIdx.x];
-#if PLEAS_WGRAD_TIMELINE
-    const long long t_start = __builtin_amdgcn_s_memrealtime();
-    if (it.layer < 0) {
-        if (threadIdx.x == 0 && blockIdx.x < 16384) {
-            g_wgrad_timeline[blockIdx.x][0] = t_start; g_wgrad_timeline[blockIdx.x][1] = t_start;
-            g_wgrad_timeline[blockIdx.x][2] = -1; g_wgrad_timeline[blockIdx.x][3] = 0;
-        }
-        return;
-    }
-#else
     if (it.layer < 0) return;   // padding of the XCD-aware item order
-#endif
     const WgradLayerDev L = layers[it.layer];
     switch (L.variant & 3) {  // block-uniform
         case 0: wgrad_dispatch<128, 128>(L, it, smem); break;
@@ -484,16 +466,6 @@ __global__ __launch_bounds__(cThreads, 2) void wgrad_batch_kernel(const WgradLay
         case 2: wgrad_dispatch<128, 64>(L, it, smem); break;
         default: wgrad_dispatch<64, 64>(L, it, smem); break;
     }
-#if PLEAS_WGRAD_TIMELINE
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 16384) {
-        const long long hw = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(63508) << 32);
-        g_wgrad_timeline[blockIdx.x][0] = t_start;
-        g_wgrad_timeline[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
-        g_wgrad_timeline[blockIdx.x][2] = hw;
-        g_wgrad_timeline[blockIdx.x][3] = (long long)(it.c_end - it.c_begin) * ((L.variant & 1) ? 64 : 128) * ((L.variant & 2) ? 64 : 128);
-    }
-#endif
 }
 
 __global__ __launch_bounds__(cThreads, 3) void wgrad_batch_split_kernel(const WgradLayerDev* __restrict__ layers,
@@ -644,12 +616,8 @@ struct WgradPlan {
 };
 // A few plans are kept (keyed by layer geometry + workspace address): a caller may alternate between grouped launches,
 // e.g. the two gradient buckets of a data-parallel update, without rebuilding and re-uploading the tables each time.
-constexpr int kWgradPlans = 4;
-static WgradPlan g_wplans[kWgradPlans];
-static unsigned g_wplan_turn = 0;
+static PlanCache<WgradPlan, 1, 4> g_wgrad_plans;      // key element 1 is the workspace address (wgrad_key)
 static std::mutex g_wplan_mu;
-
-static size_t walign(size_t v) { return (v + 255) / 256 * 256; }
 
 static int build_wgrad_plan(WgradPlan& P, const pleas_wgrad_layer* ly, int n) {
     P.layers.assign(n, WgradLayerDev());
@@ -698,11 +666,9 @@ static int build_wgrad_plan(WgradPlan& P, const pleas_wgrad_layer* ly, int n) {
         // direct Y shares X's vector width, so it also needs HWi == HWo (true for 1x1 stride 1)
         d.variant = (TM == 64 ? 1 : 0) | (TN == 64 ? 2 : 0) | (xvec ? 0 : 4) | (ydirect ? 0 : 8) | (virt ? 32 : 0);
         // stride-1 "same" k x k layers on images with HW % 4 == 0: the shifted operand comes through aligned 16-byte loads
-        // (PLEAS_WGRAD_VECSHIFT=0 keeps the one-pixel-per-load form for A/B)
-        static const bool vecshift = !(std::getenv("PLEAS_WGRAD_VECSHIFT") && std::atoi(std::getenv("PLEAS_WGRAD_VECSHIFT")) == 0);
         const int64_t total = (int64_t)l.N * l.Cin * HWi;
         d.total = 0;
-        if (vecshift && !virt && !ydirect && xvec && l.stride == 1 && l.KH == l.KW && 2 * l.pad == l.KH - 1 && HWi == HWo &&
+        if (!virt && !ydirect && xvec && l.stride == 1 && l.KH == l.KW && 2 * l.pad == l.KH - 1 && HWi == HWo &&
             total < (1ll << 31)) {
             d.variant |= 16;
             d.total = (int)total;
@@ -754,13 +720,13 @@ static int build_wgrad_plan(WgradPlan& P, const pleas_wgrad_layer* ly, int n) {
     }
     size_t off = 0;
     P.off_layers = off;
-    off = walign(off + P.layers.size() * sizeof(WgradLayerDev));
+    off = align256(off + P.layers.size() * sizeof(WgradLayerDev));
     P.off_items = off;
-    off = walign(off + P.items.size() * sizeof(WgradItemDev));
+    off = align256(off + P.items.size() * sizeof(WgradItemDev));
     P.off_bl = off;
-    off = walign(off + P.blk_layer.size() * sizeof(int));
+    off = align256(off + P.blk_layer.size() * sizeof(int));
     P.off_bb = off;
-    off = walign(off + P.blk_begin.size() * sizeof(int));
+    off = align256(off + P.blk_begin.size() * sizeof(int));
     P.off_slabs = off;
     P.total = off + slabs * sizeof(float);
     for (int i = 0; i < n; ++i) P.layers[i].slab = reinterpret_cast<float*>(slab_off[i]);
@@ -768,30 +734,8 @@ static int build_wgrad_plan(WgradPlan& P, const pleas_wgrad_layer* ly, int n) {
     return PLEAS_OK;
 }
 
-// one side stream + two events per device for the exact grid of a launch under the split arithmetic (created once per process)
-struct WgradSideStream {
-    hipStream_t stream;
-    hipEvent_t forked, joined;
-    bool ok = false;
-};
-static WgradSideStream& wgrad_side_stream() {
-    constexpr int kMaxDev = 16;
-    static WgradSideStream sets[kMaxDev];
-    static bool tried[kMaxDev] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) {
-        static WgradSideStream none;
-        return none;
-    }
-    WgradSideStream& s = sets[dev];
-    if (!tried[dev]) {
-        tried[dev] = true;
-        s.ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
-               hipEventCreateWithFlags(&s.forked, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&s.joined, hipEventDisableTiming) == hipSuccess;
-    }
-    return s;
-}
+// one side stream per device for the exact grid of a launch under the split arithmetic (the forward has a set of its own)
+static SideStreams<1> g_wgrad_side;
 
 static std::vector<int64_t> wgrad_key(const pleas_wgrad_layer* ly, int n, const void* ws) {
     std::vector<int64_t> k;
@@ -808,13 +752,6 @@ static std::vector<int64_t> wgrad_key(const pleas_wgrad_layer* ly, int n, const 
 }  // namespace pleas
 
 using namespace pleas;
-
-#if PLEAS_WGRAD_TIMELINE
-extern "C" int pleas_wgrad_timeline_read(long long* out, int max_items) {      // study builds only
-    const int n = std::min(max_items, 16384);
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgrad_timeline), (size_t)n * 4 * sizeof(long long)) == hipSuccess ? n : -1;
-}
-#endif
 
 extern "C" void pleas_wgrad_tune(int item_chunks) {
     if (item_chunks > 0) g_wgrad_item_chunks = item_chunks;
@@ -862,12 +799,9 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
     hipStream_t stream = (hipStream_t)stream_;
     std::lock_guard<std::mutex> lk(g_wplan_mu);
     std::vector<int64_t> key = wgrad_key(layers, n_layers, ws);
-    WgradPlan* hit = nullptr;
-    for (auto& cand : g_wplans)
-        if (cand.key == key) hit = &cand;
+    WgradPlan* hit = g_wgrad_plans.find(key);
     if (!hit) {
-        hit = &g_wplans[g_wplan_turn++ % kWgradPlans];
-        hit->key.clear();
+        hit = &g_wgrad_plans.take();
         const int rc = build_wgrad_plan(*hit, layers, n_layers);
         if (rc != PLEAS_OK) return rc;
         hit->key.swap(key);
@@ -881,8 +815,7 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
     }
     char* base = (char*)ws;
     if (!P.uploaded) {
-        for (auto& other : g_wplans)   // its tables go into `ws`: whatever another plan had there is gone
-            if (&other != &P && other.key.size() > 1 && other.key[1] == (int64_t)(uintptr_t)ws) other.uploaded = false;
+        g_wgrad_plans.claims_workspace(P);
         float* slab0 = reinterpret_cast<float*>(base + P.off_slabs);
         std::vector<WgradLayerDev> abs_layers = P.layers;
         for (auto& d : abs_layers) d.slab = slab0 + reinterpret_cast<size_t>(d.slab);
@@ -920,13 +853,13 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
         // 7 x 7 images, strided layers, the stem -- few, long items).  Back to back on one stream the second would start when the
         // first one's last workgroup has ended (0.39 ms for two layers alone, profiles/r05_pmc_split_3x3s1_14.txt): the exact grid
         // goes to a side stream of the library instead (fork / join with events, as the forward's forms do).
-        WgradSideStream& side = wgrad_side_stream();
+        SideStreams<1>::Set& side = g_wgrad_side.current();
         const bool fork = P.n_split > 0 && n_exact > 0 && side.ok;
         hipStream_t st_exact = stream;
         if (fork) {
             PLEAS_HIP_CHECK(hipEventRecord(side.forked, stream));
-            PLEAS_HIP_CHECK(hipStreamWaitEvent(side.stream, side.forked, 0));
-            st_exact = side.stream;
+            PLEAS_HIP_CHECK(hipStreamWaitEvent(side.streams[0], side.forked, 0));
+            st_exact = side.streams[0];
         }
         if (n_exact > 0) {
             hipLaunchKernelGGL(wgrad_batch_kernel, dim3((unsigned)n_exact), dim3(cThreads), P.lds, st_exact, dl, its + P.n_split);
@@ -937,8 +870,8 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
             PLEAS_LAUNCH_CHECK("wgrad_batch_split_kernel");
         }
         if (fork) {
-            PLEAS_HIP_CHECK(hipEventRecord(side.joined, side.stream));
-            PLEAS_HIP_CHECK(hipStreamWaitEvent(stream, side.joined, 0));
+            PLEAS_HIP_CHECK(hipEventRecord(side.joined[0], side.streams[0]));
+            PLEAS_HIP_CHECK(hipStreamWaitEvent(stream, side.joined[0], 0));
         }
         if (!P.blk_layer.empty()) {
             hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)P.blk_layer.size()), dim3(256), 0, stream, dl,

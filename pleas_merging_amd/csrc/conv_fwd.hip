@@ -27,15 +27,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fwd_schedule.hpp"
 
 namespace pleas {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef PLEAS_FWD_ABLATE
-#define PLEAS_FWD_ABLATE 0   // experiments only (tools/hipbench/run_fwd_ablate.sh): 1 no target gathers, 2 no epilogue,
-#endif                       // 4 no input-operand loads, 8 no weight loads, 16 per-item cycle stamps (pleas_fwd_debug_read)
 constexpr int fBK = 32;
 constexpr int fLdsA = 36;    // W tile rows: [TM][36]   (k contiguous)
 constexpr int fLdsB = 36;    // U tile rows: [128 pixels][36] (k contiguous: a thread's 16 k values of its pixel are one run)
@@ -69,13 +67,6 @@ struct FwdLayerDev {
 struct FwdItemDev {
     int layer, tm, tp, slot;  // slot: loss-partial index
 };
-
-#if (PLEAS_FWD_ABLATE & 16)
-__device__ long long g_fwd_stamps[32768][4];   // per work item: prologue, K loop, epilogue cycles, chunks
-#define PLEAS_FWD_STAMP(var) const long long var = clock64()
-#else
-#define PLEAS_FWD_STAMP(var)
-#endif
 
 // ---- shared by both tile forms: the block maps / biases of a tile's output channels, and the epilogue
 template <int TM, int PLAIN = 0>
@@ -114,17 +105,6 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
     const uint32_t p0 = (uint32_t)it.tp * fTN;
     // ---- epilogue.  Accumulators hold one pixel per lane; go through LDS once ([co][pixel], stride 132) so that
     //      each thread then owns 4 consecutive pixels of one output channel: 16-B target gathers, 16-B residual stores.
-    if constexpr ((PLEAS_FWD_ABLATE & 2) != 0) {   // keep the accumulators alive with one store per wave
-        float s = 0.f;
-#pragma unroll
-        for (int sm = 0; sm < MTM; ++sm)
-#pragma unroll
-            for (int sn = 0; sn < 2; ++sn)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s += acc[sm][sn][r];
-        if (s == 12345.678f) partials[L.part_base + it.slot] = s;
-        return;
-    }
     constexpr int EL = 132;
     float* Ct = smem;  // [TM][EL] floats <= the staging buffers just released by the last barrier of the K loop
     auto spill_acc = [&]() {
@@ -179,9 +159,6 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                     ta[bt][u] = has_res ? idn : f32x4{0.f, 0.f, 0.f, 0.f};
                 } else if constexpr (PLAIN) {
                     ta[bt][u] = tb[bt][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                } else if constexpr ((PLEAS_FWD_ABLATE & 1) != 0) {
-                    ta[bt][u] = f32x4{(float)(oa & 3), 0.f, 0.f, 0.f};
-                    tb[bt][u] = f32x4{(float)(ob & 3), 0.f, 0.f, 0.f};
                 } else {
                     ta[bt][u] = *(const __attribute__((address_space(1))) f32x4*)(o1b + oa);
                     tb[bt][u] = *(const __attribute__((address_space(1))) f32x4*)(o2b + ob);
@@ -276,7 +253,6 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
     constexpr int LPR = fBK / VECA, RPP = fThreads / LPR, PASS = TM / RPP;
     float* As = smem;                      // [2][TM][fLdsA]
     float* Bs = smem + 2 * TM * fLdsA;     // [2][fTN][fLdsB]
-    PLEAS_FWD_STAMP(st0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int i0 = it.tm * TM;
@@ -335,10 +311,7 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
             const uint32_t kc = kina ? k : 0u;
 #pragma unroll
             for (int q = 0; q < PASS; ++q) {
-                if constexpr ((PLEAS_FWD_ABLATE & 8) != 0) {
-#pragma unroll
-                    for (int e = 0; e < VECA; ++e) ra[q][e] = (float)(kc + e);
-                } else if constexpr (VECA == 4) {
+                if constexpr (VECA == 4) {
                     const f32x4 v = *(const __attribute__((address_space(1))) f32x4*)(PLEAS_GLOBAL(L.w) + offa[q] + kc);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ra[q][e] = v[e];
@@ -369,7 +342,6 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
                     const bool ok = ok_tap && ch < (uint32_t)L.Cin;
                     okb |= (ok ? 1u : 0u) << q;
                     const long long lin = (long long)min(ch, (uint32_t)L.Cin - 1u) * HWi;   // scalar; masked lanes read ip[lin]
-                    if constexpr ((PLEAS_FWD_ABLATE & 4) != 0) rb[q] = (float)((voff + lin) & 7); else
                     rb[q] = PLEAS_GLOBAL(L.ip)[voff + lin];
                 }
             } else {
@@ -384,7 +356,6 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
                     okb |= (ok ? 1u : 0u) << q;
                     const long long lin = (long long)ci * HWi + kh * L.Win + kw;   // scalar
                     const size_t off = (size_t)((long long)pbase + pixoff + lin) & (size_t)(-(long long)ok);
-                    if constexpr ((PLEAS_FWD_ABLATE & 4) != 0) rb[q] = (float)(off & 7); else
                     rb[q] = PLEAS_GLOBAL(L.ip)[off];
                     ++r;
                     ++kw;
@@ -444,7 +415,6 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
     load_chunk(0);
     store_chunk(0);
     __syncthreads();
-    PLEAS_FWD_STAMP(st1);
     // The block maps and biases of the epilogue are requested before the LAST chunk's MFMAs (no staging loads are in
     // flight then): their round trip is covered by that chunk instead of opening the epilogue.
     constexpr int ROWS = TM / 8;
@@ -461,18 +431,8 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
     load_maps();
     compute((nchunks - 1) & 1);
     __syncthreads();
-    PLEAS_FWD_STAMP(st2);
 
     fwd_epilogue<TM, PLAIN>(L, it, acc, m1, m2, bias_v, smem, partials);
-#if (PLEAS_FWD_ABLATE & 16)
-    if (tid == 0 && blockIdx.x < 32768) {
-        const long long st3 = clock64();
-        g_fwd_stamps[blockIdx.x][0] = st1 - st0;
-        g_fwd_stamps[blockIdx.x][1] = st2 - st1;
-        g_fwd_stamps[blockIdx.x][2] = st3 - st2;
-        g_fwd_stamps[blockIdx.x][3] = nchunks * 1000 + TM;
-    }
-#endif
 }
 
 
@@ -488,21 +448,11 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
 // have tap r reads the row's ZERO COLUMN instead (one select on the address per tap and 32-pixel fragment).
 // Weights: kernel-position-major chunks (tap r, channel block) exactly as in fwd_tile; accumulators and epilogue shared.
 constexpr int fFlatRow1 = 132;     // Bs row stride of 1x1 layers: 128 pixels + zero column, 16-B aligned rows
-constexpr int fFlatRowK = 260;     // (round 2-3 layout of the k x k image, [k][column]; kept for the 1x1 forms' sizing only)
 constexpr int fFlatPix = 36;       // k x k image since round 4: [column][36] -- a pixel's 32 channels contiguous (+ 4 pad: 16-byte
                                    // aligned rows, conflict-free ds_read_b128 as for the weight tile), so that ONE 16-byte LDS read
                                    // feeds four MFMA steps instead of four 4-byte reads (an LDS read costs the SIMD ~10 cycles
                                    // whatever its width)
 constexpr int fFlatColsK = 248;    // columns of that image: 128 + 2 * halo data columns + one zero row
-#ifndef PLEAS_FWD_TIMELINE
-#define PLEAS_FWD_TIMELINE 0   // study builds (tools/r04/timeline.sh): per work item, when and where it ran
-#endif
-#if PLEAS_FWD_TIMELINE
-__shared__ long long g_tl_phase[2];   // wall clock at the end of the prologue / of the K loop (flat forms)
-#define PLEAS_TL_PHASE(k) do { if (threadIdx.x == 0) g_tl_phase[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define PLEAS_TL_PHASE(k)
-#endif
 // KIND 0: 1x1, 16-B loads along the pixel axis (HW % 4 == 0), two images (double buffer)
 // KIND 1: 1x1, scalar loads (HW % 4 != 0, e.g. 7 x 7), two images
 // KIND 2: k x k, scalar loads, ONE image per channel block shared by all taps
@@ -614,10 +564,7 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
     auto load_a = [&](int cb, int r, f32x4 (&ra)[PASS]) {
         const uint32_t k = (uint32_t)r * L.Cin + (uint32_t)cb * fBK + acol;    // kernel-position-major (== plain for 1x1)
 #pragma unroll
-        for (int q = 0; q < PASS; ++q) {
-            if constexpr ((PLEAS_FWD_ABLATE & 8) != 0) ra[q] = f32x4{(float)(k & 3), 0.f, 1.f, 0.f}; else
-            ra[q] = *(const __attribute__((address_space(1))) f32x4*)(PLEAS_GLOBAL(L.w) + offa[q] + k);
-        }
+        for (int q = 0; q < PASS; ++q) ra[q] = *(const __attribute__((address_space(1))) f32x4*)(PLEAS_GLOBAL(L.w) + offa[q] + k);
     };
     // Tiles whose rows / pixels all exist store their staged values as they are (block-uniform tests): every select that is
     // not executed is vector-pipe time the fp32 MFMAs get back (a vector instruction costs ~4.5 cycles of it).
@@ -651,9 +598,7 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
         if constexpr (KIND == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                f32x4 v;
-                if constexpr ((PLEAS_FWD_ABLATE & 4) != 0) v = f32x4{(float)(cb & 3), 0.f, 1.f, 0.f}; else
-                v = *(const __attribute__((address_space(1))) f32x4*)(base + voff[0] + (uint32_t)(8 * i) * HW);
+                const f32x4 v = *(const __attribute__((address_space(1))) f32x4*)(base + voff[0] + (uint32_t)(8 * i) * HW);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) rb[4 * i + e] = v[e];
             }
@@ -663,10 +608,7 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
             for (int kr = 0; kr < 8; ++kr)
 #pragma unroll
                 for (int m = 0; m < MCOL; ++m)
-                    if (m < M) {
-                        if constexpr ((PLEAS_FWD_ABLATE & 4) != 0) rb[kr * MCOL + m] = (float)((cb + kr) & 3); else
-                        rb[kr * MCOL + m] = wbase[(size_t)kr * HW + voff[m]];
-                    }
+                    if (m < M) rb[kr * MCOL + m] = wbase[(size_t)kr * HW + voff[m]];
         }
     };
     auto store_b = [&](int buf, const auto& rb) {
@@ -749,13 +691,8 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
         const int delta = tap_delta(r);
         const float* a = As + abuf * TM * fLdsA + (wm * (TM / 2) + (lane & 31)) * fLdsA + 4 * (lane >> 5);
         const float* bb = Bs + bbuf * fBK * Lr + 4 * (lane >> 5) * Lr;     // half-wave h takes k = 8 kk + e + 4 h
-        // A lane whose tap falls outside the image takes 0: by a select on the value it read at its own (always valid:
-        // the halo is part of the image) address.  Reading the row's zero column instead put that lane on the bank of
-        // some other lane of its half-wave: 22 % of the k x k forms' LDS cycles were such 2-way conflicts
-        // (profiles/r03_lds_fwd_batch_rn101_before.txt).  PLEAS_FWD_ZEROCOL=1 at build time restores the zero-column read.
-#ifndef PLEAS_FWD_ZEROCOL
-#define PLEAS_FWD_ZEROCOL 0
-#endif
+        // A lane whose tap (k x k) or pixel (1 x 1: past the tensor's end) is not there takes 0 by reading the image's zero
+        // row / the row's zero column: one select on the address per tap and fragment instead of one per value.
         const bool ok0 = (tapok[0] >> r) & 1u, ok1 = (tapok[1] >> r) & 1u;
         if constexpr (SPLIT) {
             const __bf16* a16 = As16 + (wm * (TM / 2) + (lane & 31)) * kSplitRow + 8 * (lane >> 5);
@@ -821,9 +758,9 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
             }
             return;
         }
-        constexpr bool zero_col = PLEAS_FWD_ZEROCOL || KIND != 2;      // 1 x 1 forms: only pixels past the tensor's end
-        const float* b0 = bb + ((zero_col && !ok0) ? jz : jb[0] + delta);
-        const float* b1 = bb + ((zero_col && !ok1) ? jz : jb[1] + delta);
+        // the 1 x 1 forms (one tap, no shift)
+        const float* b0 = bb + (ok0 ? jb[0] : jz);
+        const float* b1 = bb + (ok1 ? jb[1] : jz);
 #pragma unroll
         for (int kk = 0; kk < fBK / 8; ++kk) {
             f32x4 fa[MTM];
@@ -831,11 +768,7 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
             for (int s = 0; s < MTM; ++s) fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * fLdsA + kk * 8);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float f0 = b0[(kk * 8 + e) * Lr], f1 = b1[(kk * 8 + e) * Lr];
-                if constexpr (!zero_col) {
-                    f0 = ok0 ? f0 : 0.f;
-                    f1 = ok1 ? f1 : 0.f;
-                }
+                const float f0 = b0[(kk * 8 + e) * Lr], f1 = b1[(kk * 8 + e) * Lr];
 #pragma unroll
                 for (int sm = 0; sm < MTM; ++sm) {
                     acc[sm][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], f0, acc[sm][0], 0, 0, 0);
@@ -858,7 +791,6 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
     store_a(0, ra0);
     store_b(0, rb0);
     __syncthreads();
-    PLEAS_TL_PHASE(0);
     constexpr int ROWS = TM / 8;
     int m1[ROWS], m2[ROWS];
     float bias_v[ROWS];
@@ -929,100 +861,85 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
     fwd_load_maps<TM, PLAIN>(L, i0, m1, m2, bias_v);        // epilogue operands, requested under the last chunk's MFMAs
     compute((nchunks - 1) & 1, bsel, r);
     __syncthreads();
-    PLEAS_TL_PHASE(1);
     fwd_epilogue<TM, PLAIN>(L, it, acc, m1, m2, bias_v, smem, partials);
 }
 
 // One kernel per tile form (register allocation and LDS are then per form, not the maximum over all of them); the host
-// launches each form's slice of the item list.  Form ids: 0-3 = fwd_tile<128,4>, <64,4>, <128,1>, <64,1>;
-// 4-6 = fwd_flat_tile<128, KIND 0-2>;  7-9 = fwd_flat_tile<64, KIND 0-2>.
+// launches each form's slice of the item list.  The form ids are ABI (pleas_fwd_plan_units, pleas_fwd_plan_lanes); what a
+// form IS stands in this table and nowhere else.
+struct FwdForm {
+    bool flat;        // fwd_flat_tile, else the general fwd_tile
+    int tm;           // output channels of a tile
+    int sub;          // general: floats per weight load (VECA); flat: KIND
+    bool split;       // a split-bf16 kernel exists (launched under pleas_arith(PLEAS_ARITH_SPLIT_BF16); the other forms run
+                      // their exact kernel in the same launch group)
+    int occupancy[2]; // workgroups per CU the exact / the split kernel is compiled for
+    double weight;    // expected duration per unit of MFMA work (measured on the ResNet-101 list, each form alone): the general
+                      // tile (stride-2 layers: few, long items; stem: scalar weight loads) runs at ~0.4x the flat forms' rate,
+                      // the scalar-pixel 1 x 1 form (7 x 7 images) at ~0.5x
+};
 constexpr int fForms = 10;
-#if PLEAS_FWD_TIMELINE
-__device__ long long g_fwd_timeline[32768][4];   // start, end (100 MHz wall clock), flat forms: prologue | K loop << 32 [ticks], form | chunks * TM << 8
-__device__ int g_fwd_timeline_n;
-#endif
-// SPLIT = 1: the split-bf16 variant of a flat form (4, 6, 7, 9: KIND 0 / 2), launched instead of the exact one when the plan
-// was built under pleas_arith(PLEAS_ARITH_SPLIT_BF16); every other form runs the exact arithmetic in the same launch group.
-constexpr bool fwd_form_splits(int form) { return form == 4 || form == 6 || form == 7 || form == 9; }
+constexpr FwdForm kFwdForms[fForms] = {
+    {false, 128, 4, false, {2, 2}, 2.5}, {false, 64, 4, false, {2, 2}, 2.5},
+    {false, 128, 1, false, {2, 2}, 2.5}, {false, 64, 1, false, {2, 2}, 2.5},
+    {true, 128, 0, true, {2, 2}, 1.0},   {true, 128, 1, false, {2, 2}, 2.0}, {true, 128, 2, true, {2, 2}, 1.0},
+    {true, 64, 0, true, {2, 3}, 1.0},    {true, 64, 1, false, {2, 2}, 2.0},  {true, 64, 2, true, {2, 3}, 1.0},
+};
+// the id of FwdLayerDev::variant's form
+constexpr int fwd_form_of(int variant) {
+    if (variant & 8) return ((variant & 1) ? 7 : 4) + ((variant >> 4) & 3);
+    return variant & 3;
+}
+// row f of the table describes what fwd_describe's variant bits call form f
+constexpr bool fwd_forms_match_variants() {
+    for (int f = 0; f < fForms; ++f) {
+        const FwdForm& F = kFwdForms[f];
+        const int variant = (F.tm == 64 ? 1 : 0) | (F.flat ? 8 | (F.sub << 4) : (F.sub == 1 ? 2 : 0));
+        if (fwd_form_of(variant) != f || (F.split && !(F.flat && F.sub != 1))) return false;
+    }
+    return true;
+}
+static_assert(fwd_forms_match_variants(), "kFwdForms is indexed by the form id");
 template <int FORM, int SPLIT = 0>
-__global__ __launch_bounds__(fThreads, (SPLIT && FORM >= 7) ? 3 : 2) void fwd_batch_kernel(const FwdLayerDev* __restrict__ layers,
+__global__ __launch_bounds__(fThreads, kFwdForms[FORM].occupancy[SPLIT]) void fwd_batch_kernel(const FwdLayerDev* __restrict__ layers,
                                                              const FwdItemDev* __restrict__ items,
                                                              float* __restrict__ partials) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const FwdItemDev it = items[blockIdx.x];
     if (it.layer < 0) return;   // padding of the XCD-aware item order
     const FwdLayerDev L = layers[it.layer];
-#if PLEAS_FWD_TIMELINE
-    struct Stamp {
-        long long t0; int form; long long work;
-        __device__ ~Stamp() {
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const int slot = atomicAdd(&g_fwd_timeline_n, 1);
-                if (slot < 32768) {
-                    g_fwd_timeline[slot][0] = t0;
-                    g_fwd_timeline[slot][1] = __builtin_amdgcn_s_memrealtime();
-                    g_fwd_timeline[slot][2] = form >= 4 ? ((g_tl_phase[0] - t0) | ((g_tl_phase[1] - t0) << 32)) : 0;
-                    g_fwd_timeline[slot][3] = form | (work << 8);
-                }
-            }
-        }
-    } stamp{(long long)__builtin_amdgcn_s_memrealtime(), FORM,
-            (long long)((L.Kd + fBK - 1) / fBK) * ((L.variant & 1) ? 64 : 128)};
-#endif
-    if constexpr (FORM == 0) fwd_tile<128, 4>(L, it, smem, partials);
-    else if constexpr (FORM == 1) fwd_tile<64, 4>(L, it, smem, partials);
-    else if constexpr (FORM == 2) fwd_tile<128, 1>(L, it, smem, partials);
-    else if constexpr (FORM == 3) fwd_tile<64, 1>(L, it, smem, partials);
-    else if constexpr (FORM < 7) fwd_flat_tile<128, FORM - 4, SPLIT>(L, it, smem, partials);
-    else fwd_flat_tile<64, FORM - 7, SPLIT>(L, it, smem, partials);
+    constexpr FwdForm F = kFwdForms[FORM];
+    if constexpr (F.flat) fwd_flat_tile<F.tm, F.sub, SPLIT>(L, it, smem, partials);
+    else fwd_tile<F.tm, F.sub>(L, it, smem, partials);
 }
 // A plain convolution (pleas_conv2d_fwd): ONE layer, described in the kernel arguments; the work item is the block index
 // (output-channel tile fastest, as in the grouped plan), no tables, no target, no loss.
 template <int FORM, int SPLIT = 0, int BN = 0>
-__global__ __launch_bounds__(fThreads, (SPLIT && FORM >= 7) ? 3 : 2) void conv2d_fwd_kernel(const FwdLayerDev L, const int tms) {
+__global__ __launch_bounds__(fThreads, kFwdForms[FORM].occupancy[SPLIT]) void conv2d_fwd_kernel(const FwdLayerDev L, const int tms) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const FwdItemDev it{0, (int)(blockIdx.x % (unsigned)tms), (int)(blockIdx.x / (unsigned)tms), 0};
+    constexpr FwdForm F = kFwdForms[FORM];
     constexpr int PLAIN = 1 + BN;      // 2: the BatchNorm / add / ReLU image is written beside the output
-    if constexpr (FORM == 0) fwd_tile<128, 4, PLAIN>(L, it, smem, nullptr);
-    else if constexpr (FORM == 1) fwd_tile<64, 4, PLAIN>(L, it, smem, nullptr);
-    else if constexpr (FORM == 2) fwd_tile<128, 1, PLAIN>(L, it, smem, nullptr);
-    else if constexpr (FORM == 3) fwd_tile<64, 1, PLAIN>(L, it, smem, nullptr);
-    else if constexpr (FORM < 7) fwd_flat_tile<128, FORM - 4, SPLIT, PLAIN>(L, it, smem, nullptr);
-    else fwd_flat_tile<64, FORM - 7, SPLIT, PLAIN>(L, it, smem, nullptr);
+    if constexpr (F.flat) fwd_flat_tile<F.tm, F.sub, SPLIT, PLAIN>(L, it, smem, nullptr);
+    else fwd_tile<F.tm, F.sub, PLAIN>(L, it, smem, nullptr);
 }
-// side streams + events of the library for the concurrent forms (created once per process; no device memory)
-constexpr int fLanes = 3;          // side streams (+ the caller's stream = four hardware queues)
-struct FwdSideStreams {
-    hipStream_t streams[fLanes];
-    hipEvent_t forked, joined[fLanes];
-    bool ok = false;
+// The kernels of a form, [split arithmetic]: a form without a split kernel keeps its exact one there.
+struct FwdFormKernels {
+    void (*batch[2])(const FwdLayerDev*, const FwdItemDev*, float*);
+    void (*conv2d[2][2])(const FwdLayerDev, const int);      // [BN][split arithmetic]
 };
-static FwdSideStreams& fwd_side_streams() {
-    // one set per device (streams belong to the device that was current when they were created)
-    constexpr int kMaxDev = 16;
-    static FwdSideStreams sets[kMaxDev];
-    static bool tried[kMaxDev] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) {
-        static FwdSideStreams none;      // ok == false: the forms go back to back on the caller's stream
-        return none;
-    }
-    FwdSideStreams& s = sets[dev];
-    if (!tried[dev]) {
-        tried[dev] = true;
-        bool ok = hipEventCreateWithFlags(&s.forked, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; ok && i < fLanes; ++i)
-            ok = hipStreamCreateWithFlags(&s.streams[i], hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&s.joined[i], hipEventDisableTiming) == hipSuccess;
-        s.ok = ok;
-    }
-    return s;
+template <int FORM>
+static constexpr FwdFormKernels fwd_form_kernels() {
+    constexpr int S = kFwdForms[FORM].split ? 1 : 0;
+    return {{fwd_batch_kernel<FORM, 0>, fwd_batch_kernel<FORM, S>},
+            {{conv2d_fwd_kernel<FORM, 0, 0>, conv2d_fwd_kernel<FORM, S, 0>}, {conv2d_fwd_kernel<FORM, 0, 1>, conv2d_fwd_kernel<FORM, S, 1>}}};
 }
-static inline int fwd_form_of(int variant) {
-    if (variant & 8) return ((variant & 1) ? 7 : 4) + ((variant >> 4) & 3);
-    return variant & 3;
-}
+static const FwdFormKernels kFwdKernels[fForms] = {fwd_form_kernels<0>(), fwd_form_kernels<1>(), fwd_form_kernels<2>(), fwd_form_kernels<3>(),
+                                                   fwd_form_kernels<4>(), fwd_form_kernels<5>(), fwd_form_kernels<6>(), fwd_form_kernels<7>(),
+                                                   fwd_form_kernels<8>(), fwd_form_kernels<9>()};
+// side streams of the library for the concurrent forms (+ the caller's stream = four hardware queues)
+constexpr int fLanes = 3;
+static SideStreams<fLanes> g_fwd_side;
 
 // loss[l] = scale[l] * sum of this layer's partials (fixed order, fp64 combine)
 struct FwdLossDev {
@@ -1076,161 +993,30 @@ struct FwdPlan {
     int form_begin[fForms] = {0}, form_count[fForms] = {0};
     size_t form_lds[fForms] = {0};
     std::vector<float> item_work;      // per item (aligned with `items`): relative duration, 0 for padding
-    // A launch UNIT is a form's kernel over a contiguous slice of the form's items.  At first every form is one unit; after
-    // the calibration launch a form that alone would outlast a lane's fair share is cut into slices of equal work.
-    struct Unit { int form, begin, count, lane; double ms; };
-    std::vector<Unit> units;           // in launch order (longest first)
+    std::vector<FwdUnit> units;        // in launch order (fwd_schedule.hpp)
     double flops = 0, bytes = 0;
     int n_parts = 0;
     bool uploaded = false;
     bool split = false;                // built under pleas_arith(PLEAS_ARITH_SPLIT_BF16): the flat forms launch their split kernels
-    // lanes from MEASURED durations: launch kCalibAt of a plan brackets every form's kernel with events on its lane; a
+    // lanes from MEASURED durations: launch kFwdCalibAt of a plan brackets every unit's kernel with events on its lane; a
     // later launch that finds them complete deals the forms again, longest measured duration first
     int launches = 0, calib = 0;       // calib: 0 not measured yet, 1 events recorded, 2 lanes dealt from measurements
     // the calibration launch's events, around every unit's kernel on its lane.  They belong to the PLAN (a slot of the plan
     // cache, alive for the process): two plans that calibrate at the same time must not read each other's timings.
-    hipEvent_t t0[24], t1[24];
+    hipEvent_t t0[kFwdMaxUnits], t1[kFwdMaxUnits];
     int timed = 0;                     // 0 events not created yet, 1 created, -1 creation failed (no calibration)
     bool timing_events() {
         if (timed == 0) {
             timed = 1;
-            for (int u = 0; u < 24 && timed == 1; ++u)
+            for (int u = 0; u < kFwdMaxUnits && timed == 1; ++u)
                 if (hipEventCreate(&t0[u]) != hipSuccess || hipEventCreate(&t1[u]) != hipSuccess) timed = -1;
         }
         return timed == 1;
     }
+    FwdFormItems form_items() const { return FwdFormItems{fForms, form_begin, form_count, item_work.data()}; }
 };
-constexpr int fMaxUnits = 24;
 static PlanCache<FwdPlan, 1> g_fplans;
-constexpr int kCalibAt = 3;
-// measured durations per layer-list geometry (the plan key without its workspace address): a new fitter on the same
-// layers -- every job of a bench run -- starts from the lanes the previous one measured
-static std::vector<std::pair<std::vector<int64_t>, std::vector<FwdPlan::Unit>>> g_fcalib;
-static std::vector<int64_t> fwd_geometry_key(const std::vector<int64_t>& key) {
-    std::vector<int64_t> g(key);
-    if (g.size() > 1) g[1] = 0;      // key[1] is the workspace address
-    return g;
-}
-
-// longest-processing-time first over the units' expected durations: the longest unit keeps the caller's stream (lane 0) and
-// is launched first, every other unit goes to the lane that is least loaded so far
-static void fwd_deal_lanes(FwdPlan& P) {
-    std::stable_sort(P.units.begin(), P.units.end(), [](const FwdPlan::Unit& a, const FwdPlan::Unit& b) { return a.ms > b.ms; });
-    double load[fLanes + 1] = {0};
-    for (size_t o = 0; o < P.units.size(); ++o) {
-        int best = 0;
-        for (int l = 1; l <= fLanes; ++l)
-            if (load[l] < load[best]) best = l;
-        if (o == 0) best = 0;
-        P.units[o].lane = best;
-        load[best] += P.units[o].ms;
-    }
-}
-// After the calibration launch (measured duration per form).  What the in-job timelines showed: a form with few long items
-// (stride-2 layers, the 7 x 7 layers: 400 - 900 items for 512 workgroup slots) needs WALL time whatever runs beside it,
-// while the form with the most items (1 x 1 layers with K <= 256: 20 000 short ones) soaks up whatever the chip has left.
-// So: (1) every form but that FILLER is cut into slices of equal work if it outlasts 0.7 of a lane's fair share, and the
-// units are list-scheduled onto the least-loaded lane in ascending order of their form's item count -- low parallelism
-// first; (2) the filler is cut into one slice per lane, sized so that all lanes end together, launched last on each.
-static void fwd_slice_by_work(const FwdPlan& P, const FwdPlan::Unit& u, const std::vector<double>& share, std::vector<FwdPlan::Unit>& out) {
-    double work = 0, want = 0;
-    for (int i = 0; i < u.count; ++i) work += P.item_work[u.begin + i];
-    for (double v : share) want += v;
-    int begin = u.begin;
-    double acc = 0, upto = 0;
-    size_t final_slice = 0;          // the last slice with a share takes what rounding left over
-    for (size_t k = 0; k < share.size(); ++k)
-        if (share[k] > 0) final_slice = k;
-    if (!(want > 0) || !(work > 0)) {      // nothing to divide by: the unit stays whole (on the first lane that wanted a share)
-        out.push_back(FwdPlan::Unit{u.form, u.begin, u.count, (int)final_slice, u.ms});
-        return;
-    }
-    for (size_t k = 0; k < share.size(); ++k) {
-        upto += work * share[k] / want;
-        int end = begin;
-        while (end < u.begin + u.count && share[k] > 0 && (k == final_slice || acc + P.item_work[end] <= upto)) acc += P.item_work[end++];
-        if (end == begin && share[k] > 0 && end < u.begin + u.count) acc += P.item_work[end++];
-        if (end > begin)                   // never a slice without items (a 0-block grid is an invalid launch)
-            out.push_back(FwdPlan::Unit{u.form, begin, end - begin, (int)k, u.ms * share[k] / want});   // lane field: slice index
-        begin = end;
-    }
-}
-// every form's slices must tile [form_begin, form_begin + form_count) exactly, each with at least one item
-static bool fwd_units_cover(const FwdPlan& P) {
-    for (int f = 0; f < fForms; ++f) {
-        std::vector<std::pair<int, int>> sl;
-        for (const auto& u : P.units)
-            if (u.form == f) {
-                if (u.count <= 0 || u.lane < 0 || u.lane > fLanes) return false;
-                sl.emplace_back(u.begin, u.count);
-            }
-        std::sort(sl.begin(), sl.end());
-        int at = P.form_begin[f];
-        for (const auto& s2 : sl) {
-            if (s2.first != at) return false;
-            at += s2.second;
-        }
-        if (at != P.form_begin[f] + P.form_count[f]) return false;
-    }
-    return true;
-}
-// Returns false -- and leaves the plan's units as they were -- when the measurements are unusable (an event that failed to
-// time: ms <= 0) or the result would not launch every item exactly once; the caller then keeps the static lanes.
-static bool fwd_schedule_measured(FwdPlan& P) {
-    double total = 0;
-    for (const auto& u : P.units) {
-        if (!(u.ms > 0)) return false;
-        total += u.ms;
-    }
-    if (!(total > 0)) return false;
-    const std::vector<FwdPlan::Unit> before = P.units;
-    const double fair = total / (fLanes + 1);
-    int filler = -1;
-    for (size_t i = 0; i < P.units.size(); ++i)
-        if (filler < 0 || P.units[i].count > P.units[filler].count) filler = (int)i;
-    if (filler >= 0 && (P.units[filler].ms < 0.15 * total || P.units[filler].count < 8 * (fLanes + 1))) filler = -1;
-    // (1) the other forms, long ones in equal slices
-    std::vector<FwdPlan::Unit> rest;
-    for (size_t ui = 0; ui < P.units.size(); ++ui) {
-        if ((int)ui == filler) continue;
-        const FwdPlan::Unit u = P.units[ui];
-        int parts = (u.ms > 0.7 * fair && u.count >= 64) ? (int)std::min<double>(4.0, std::ceil(u.ms / (0.45 * fair))) : 1;
-        const int room = fMaxUnits - (fLanes + 1) - (int)rest.size() - (int)(P.units.size() - ui - 1);
-        parts = std::max(1, std::min(parts, room));
-        if (parts <= 1) rest.push_back(u);
-        else fwd_slice_by_work(P, u, std::vector<double>(parts, 1.0), rest);
-    }
-    std::stable_sort(rest.begin(), rest.end(), [&](const FwdPlan::Unit& a, const FwdPlan::Unit& b) {
-        return P.form_count[a.form] != P.form_count[b.form] ? P.form_count[a.form] < P.form_count[b.form] : a.ms > b.ms;
-    });
-    double load[fLanes + 1] = {0};
-    for (size_t o = 0; o < rest.size(); ++o) {
-        int best = 0;
-        for (int l = 1; l <= fLanes; ++l)
-            if (load[l] < load[best]) best = l;
-        rest[o].lane = best;
-        load[best] += rest[o].ms;
-    }
-    // (2) the filler levels the lanes
-    if (filler >= 0) {
-        const FwdPlan::Unit f = P.units[filler];
-        double sum = f.ms;
-        for (double v : load) sum += v;
-        const double level = sum / (fLanes + 1);
-        std::vector<double> share(fLanes + 1);
-        for (int l = 0; l <= fLanes; ++l) share[l] = std::max(0.0, level - load[l]);
-        std::vector<FwdPlan::Unit> slices;
-        fwd_slice_by_work(P, f, share, slices);
-        for (auto& sl : slices)
-            if (sl.count > 0) rest.push_back(sl);      // .lane = slice index = the lane it levels
-    }
-    P.units.swap(rest);
-    if (!fwd_units_cover(P)) {
-        P.units = before;
-        return false;
-    }
-    return true;
-}
+static FwdCalibStore g_fcalib;
 
 // Geometry checks, tile height, tile form and LDS bytes of ONE layer (shared by the grouped plan and the plain convolution).
 static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_bytes, int& TM_out) {
@@ -1250,10 +1036,9 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
     // short-K layers (1x1 with few input channels) are bound by their epilogue's memory traffic, not by the MFMAs:
     // 64-row tiles (52 KB of LDS, <= 132 registers) let THREE workgroups share a CU and overlap more of it
     // (round 5: 128-row tiles for them too are 1.6 % faster per launch group in both arithmetics -- half the tiles re-read and, under
-    // the split arithmetic, re-convert each input chunk -- so the threshold is 0 unless PLEAS_FWD_TM64_K says otherwise:
-    // 2.570 -> 2.529 ms exact, 1.884 -> 1.837 ms split, profiles/r05_exp_source_conv.txt; 64-row tiles remain for Cout <= 64)
-    static const int tm64_k = std::getenv("PLEAS_FWD_TM64_K") ? std::atoi(std::getenv("PLEAS_FWD_TM64_K")) : 0;
-    const int TM = (l.Cout > 64 && !(l.KH * l.KW == 1 && l.stride == 1 && Kd <= tm64_k && l.Cin % fBK == 0)) ? 128 : 64;
+    // the split arithmetic, re-convert each input chunk: 2.570 -> 2.529 ms exact, 1.884 -> 1.837 ms split,
+    // profiles/r05_exp_source_conv.txt -- so 64-row tiles remain for Cout <= 64 only)
+    const int TM = l.Cout > 64 ? 128 : 64;
     d.variant = (TM == 64 ? 1 : 0) | (Kd % 4 == 0 ? 0 : 2);
     if (l.flags & PLEAS_FWD_KPOS_MAJOR) {
         if (l.Cin % fBK != 0) return bad_arg("conv_fwd: kernel-position-major weights need Cin % 32 == 0");
@@ -1263,7 +1048,6 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
     {
         // flat-shift form: stride 1, square odd kernel with "same" padding, whole 32-channel blocks, and (for k > 1)
         // kernel-position-major weights; its LDS must not exceed the general form's (two workgroups per CU)
-        static const bool flat_on = !(std::getenv("PLEAS_FWD_FLAT") && std::atoi(std::getenv("PLEAS_FWD_FLAT")) == 0);
         const int R = l.KH * l.KW;
         const bool same = l.stride == 1 && l.KH == l.KW && (l.KH & 1) && l.pad == (l.KH - 1) / 2;
         const int halo = l.pad * (l.Win + 1);
@@ -1271,7 +1055,7 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
         const int Lr = kind == 2 ? fFlatColsK : fFlatRow1;      // k x k: columns of the [column][36] image, zero row included
         const size_t flat_lds = std::max((size_t)(2 * TM * fLdsA + (kind == 2 ? fFlatColsK * fFlatPix : 2 * fBK * Lr)) * sizeof(float),
                                          (size_t)TM * 132 * sizeof(float));
-        if (flat_on && same && l.Cin % fBK == 0 && R <= 32 && (R == 1 || (l.flags & PLEAS_FWD_KPOS_MAJOR)) &&
+        if (same && l.Cin % fBK == 0 && R <= 32 && (R == 1 || (l.flags & PLEAS_FWD_KPOS_MAJOR)) &&
             fTN + 2 * halo < Lr && flat_lds <= lds_bytes && (int64_t)l.N * l.Cin * HWo < (1ll << 32)) {
             d.variant |= 8 | (kind << 4);
             lds_bytes = flat_lds;
@@ -1288,7 +1072,6 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
 }
 
 static std::mutex g_fplan_mu;
-static size_t falign(size_t v) { return (v + 255) / 256 * 256; }
 
 static int build_fwd_plan(FwdPlan& P, const pleas_fwd_layer* ly, int n) {
     P.split = arith_mode() == 1;
@@ -1311,25 +1094,23 @@ static int build_fwd_plan(FwdPlan& P, const pleas_fwd_layer* ly, int n) {
         d.part_base = parts;
         const int tms = (int)ceil_div(l.Cout, TM), tps = (int)ceil_div(Ptot, fTN);
         int slot = 0;
-        // Within a layer the output-channel tile runs fastest (PLEAS_FWD_ORDER=3 restores pixel-tile-fastest): with
-        // workgroup b on XCD b % 8, an XCD then keeps meeting the same few weight tiles, which stay in its L2, while
-        // every input tile is streamed once per XCD that needs it.
-        static const bool tp_major = !(std::getenv("PLEAS_FWD_ORDER") && std::atoi(std::getenv("PLEAS_FWD_ORDER")) == 3);
-        for (int outer = 0; outer < (tp_major ? tps : tms); ++outer)
-            for (int inner = 0; inner < (tp_major ? tms : tps); ++inner) {
-                const int tm = tp_major ? inner : outer, tp = tp_major ? outer : inner;
+        // Within a layer the output-channel tile runs fastest: with workgroup b on XCD b % 8, an XCD then keeps meeting the
+        // same few weight tiles, which stay in its L2, while every input tile is streamed once per XCD that needs it.
+        const int form = fwd_form_of(d.variant);
+        for (int tp = 0; tp < tps; ++tp)
+            for (int tm = 0; tm < tms; ++tm) {
                 XcdWork<FwdItemDev> w;
                 w.it = FwdItemDev{i, tm, tp, slot++};
                 w.w = (double)ceil_div(Kd, fBK) * TM;
                 // all items of a layer re-read its weights (and, across tm, its input): keep them on one XCD; layers
                 // with many pixel tiles are cut into runs of 32 tiles so that the 8 queues still balance
                 w.key = (int64_t)i * 65536 + tp / 32;
-                work[fwd_form_of(d.variant)].push_back(w);
-                form_work[fwd_form_of(d.variant)] += w.w;
+                work[form].push_back(w);
+                form_work[form] += w.w;
             }
         P.loss[i] = FwdLossDev{parts, slot, l.loss_scale, 0};
         parts += slot;
-        P.form_lds[fwd_form_of(d.variant)] = std::max(P.form_lds[fwd_form_of(d.variant)], lds_bytes);
+        P.form_lds[form] = std::max(P.form_lds[form], lds_bytes);
         P.flops += 2.0 * l.Cout * (double)Kd * (double)Ptot;
         P.bytes += ((double)l.Cin * l.N * l.Hin * l.Win + 3.0 * l.Cout * (double)Ptot) * sizeof(float);
     }
@@ -1339,25 +1120,6 @@ static int build_fwd_plan(FwdPlan& P, const pleas_fwd_layer* ly, int n) {
     for (int f = 0; f < fForms; ++f) {
         P.form_begin[f] = (int)P.items.size();
         std::vector<FwdItemDev> part = xcd_order_items(work[f], FwdItemDev{-1, 0, 0, 0}, /*by_default=*/false);
-        if (const char* env = std::getenv("PLEAS_FWD_ORDER")) {   // experiments: 1 = pseudo-random order, 2 = long / short interleaved
-            const int mode = std::atoi(env);
-            if (mode == 1) {
-                uint64_t st = 0x9E3779B97F4A7C15ull;
-                for (size_t i = part.size(); i > 1; --i) {
-                    st = st * 6364136223846793005ull + 1442695040888963407ull;
-                    std::swap(part[i - 1], part[(size_t)((st >> 33) % i)]);
-                }
-            } else if (mode == 2) {   // longest-first list folded: item k from the front, then item k from the back
-                std::vector<FwdItemDev> folded;
-                folded.reserve(part.size());
-                size_t lo = 0, hi = part.size();
-                while (lo < hi) {
-                    folded.push_back(part[lo++]);
-                    if (lo < hi) folded.push_back(part[--hi]);
-                }
-                part.swap(folded);
-            }
-        }
         P.items.insert(P.items.end(), part.begin(), part.end());
         P.form_count[f] = (int)part.size();
     }
@@ -1365,57 +1127,34 @@ static int build_fwd_plan(FwdPlan& P, const pleas_fwd_layer* ly, int n) {
     for (size_t k = 0; k < P.items.size(); ++k)
         if (P.items[k].layer >= 0) {
             const FwdLayerDev& d = P.layers[P.items[k].layer];
-            P.item_work[k] = (float)(ceil_div(d.Kd, fBK) * ((d.variant & 1) ? 64 : 128));
+            P.item_work[k] = (float)(ceil_div(d.Kd, fBK) * kFwdForms[fwd_form_of(d.variant)].tm);
         }
-    // launch order: the form with the most work first (its tail is then covered by nothing, the small ones' tails are short)
-    // Expected duration of a form relative to its MFMA work (measured on the ResNet-101 list, each form alone): the
-    // general tile (stride-2 layers: few, long items; stem: scalar weight loads) runs at ~0.4x the flat forms' rate, the
-    // scalar-pixel 1x1 form (7x7 images) at ~0.5x.
-    // These static weights deal the FIRST launches of a plan only; launch kCalibAt measures every form on its lane and the
-    // lanes are dealt again from those durations (pleas_fwd_batch).
+    // launch order: the form with the most work first (its tail is then covered by nothing, the small ones' tails are short).
+    // The forms' static weights deal the FIRST launches of a plan only; launch kFwdCalibAt measures every form on its lane and
+    // the lanes are dealt again from those durations (pleas_fwd_batch).
     P.units.clear();
     for (int f = 0; f < fForms; ++f)
         if (P.form_count[f] > 0)
-            P.units.push_back(FwdPlan::Unit{f, P.form_begin[f], P.form_count[f], 0,
-                                            form_work[f] * (f < 4 ? 2.5 : ((f == 5 || f == 8) ? 2.0 : 1.0))});
-    fwd_deal_lanes(P);
+            P.units.push_back(FwdUnit{f, P.form_begin[f], P.form_count[f], 0, form_work[f] * kFwdForms[f].weight});
+    fwd_deal_lanes(P.units, fLanes + 1);
     P.launches = P.calib = 0;
     P.n_parts = parts;
     size_t off = 0;
     P.off_layers = off;
-    off = falign(off + P.layers.size() * sizeof(FwdLayerDev));
+    off = align256(off + P.layers.size() * sizeof(FwdLayerDev));
     P.off_items = off;
-    off = falign(off + P.items.size() * sizeof(FwdItemDev));
+    off = align256(off + P.items.size() * sizeof(FwdItemDev));
     P.off_loss = off;
-    off = falign(off + P.loss.size() * sizeof(FwdLossDev));
+    off = align256(off + P.loss.size() * sizeof(FwdLossDev));
     P.off_parts = off;
     P.total = off + (size_t)parts * sizeof(float);
     P.uploaded = false;
     return PLEAS_OK;
 }
 
-#if PLEAS_FWD_TIMELINE
-extern "C" int pleas_fwd_timeline_read(long long* out, int max_items) {      // study builds only; resets the record
-    int n = 0;
-    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_fwd_timeline_n), sizeof(int)) != hipSuccess) return -1;
-    n = std::min(std::min(n, max_items), 32768);
-    if (n > 0 && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fwd_timeline), (size_t)n * 4 * sizeof(long long)) != hipSuccess) return -1;
-    const int zero = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fwd_timeline_n), &zero, sizeof(int));
-    return n;
-}
-#endif
-
 }  // namespace pleas
 
 using namespace pleas;
-
-#if (PLEAS_FWD_ABLATE & 16)
-extern "C" int pleas_fwd_debug_read(long long* out, int n_items) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fwd_stamps), sizeof(long long) * 4 * (size_t)std::min(n_items, 32768)) == hipSuccess
-               ? 0 : 1;
-}
-#endif
 
 extern "C" int pleas_fwd_plan_lanes(double* form_ms, int* form_lane, int* form_items) {
     if (!form_ms || !form_lane || !form_items) return bad_arg("fwd_plan_lanes: null pointer");
@@ -1441,7 +1180,7 @@ extern "C" int pleas_fwd_plan_units(const pleas_fwd_layer* layers, int n_layers,
     if (rc != PLEAS_OK) return rc;
     if (form_ms) {       // as if the calibration launch had measured these per-form durations
         for (auto& u : tmp.units) u.ms = form_ms[u.form];
-        (void)fwd_schedule_measured(tmp);      // unusable measurements: the static units stay
+        (void)fwd_schedule_measured(tmp.units, tmp.form_items(), fLanes + 1, kFwdMaxUnits);      // unusable measurements: the static units stay
     }
     const int n = (int)std::min<size_t>(tmp.units.size(), (size_t)max_units);
     for (int i = 0; i < n; ++i) {
@@ -1488,28 +1227,7 @@ static int conv2d_launch(const float* x, const float* w, const float* bias, floa
     const double out_floats = (double)Cout * d.Ptot;
     ProfScope prof(kProfConv2d, 2.0 * Cout * (double)d.Kd * (double)d.Ptot,
                    ((double)Cin * N * Hin * Win + out_floats * (bn ? (res ? 3.0 : 2.0) : 1.0)) * sizeof(float), st);
-    const int form = fwd_form_of(d.variant);
-    const bool split = arith_mode() == 1 && fwd_form_splits(form);
-#define PLEAS_CONV_LAUNCH(F, S, B) case F: hipLaunchKernelGGL((conv2d_fwd_kernel<F, S, B>), grid, dim3(fThreads), lds, st, d, tms); break
-#define PLEAS_CONV_FORMS(B)                                                                                              \
-    if (split) {                                                                                                         \
-        switch (form) {                                                                                                  \
-            PLEAS_CONV_LAUNCH(4, 1, B); PLEAS_CONV_LAUNCH(6, 1, B); PLEAS_CONV_LAUNCH(7, 1, B); PLEAS_CONV_LAUNCH(9, 1, B); \
-        }                                                                                                                \
-    } else {                                                                                                             \
-        switch (form) {                                                                                                  \
-            PLEAS_CONV_LAUNCH(0, 0, B); PLEAS_CONV_LAUNCH(1, 0, B); PLEAS_CONV_LAUNCH(2, 0, B); PLEAS_CONV_LAUNCH(3, 0, B); \
-            PLEAS_CONV_LAUNCH(4, 0, B); PLEAS_CONV_LAUNCH(5, 0, B); PLEAS_CONV_LAUNCH(6, 0, B); PLEAS_CONV_LAUNCH(7, 0, B); \
-            PLEAS_CONV_LAUNCH(8, 0, B); PLEAS_CONV_LAUNCH(9, 0, B);                                                      \
-        }                                                                                                                \
-    }
-    if (bn) {
-        PLEAS_CONV_FORMS(1)
-    } else {
-        PLEAS_CONV_FORMS(0)
-    }
-#undef PLEAS_CONV_FORMS
-#undef PLEAS_CONV_LAUNCH
+    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? 1 : 0][arith_mode() == 1 ? 1 : 0], grid, dim3(fThreads), lds, st, d, tms);
     PLEAS_LAUNCH_CHECK("conv2d_fwd_kernel");
     return PLEAS_OK;
 }
@@ -1525,6 +1243,59 @@ extern "C" int pleas_conv2d_bn_act_fwd(const float* x, const float* w, const flo
                                        int Win, int Cout, int KH, int KW, int stride, int pad, int flags, void* stream_) {
     if (!scale || !shift || !z) return bad_arg("conv2d_bn_act_fwd: null pointer");
     return conv2d_launch(x, w, bias, y, scale, shift, res, z, relu, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_);
+}
+
+// The calibration launch's events: all complete?  Then the plan's units take their measured durations, long ones are cut and
+// the lanes dealt again, and the result is published for other fitters on the same geometry.
+static void fwd_adopt_measurements(FwdPlan& P) {
+    if (P.calib != 1) return;
+    const int active = (int)P.units.size();
+    bool ready = true;
+    for (int u = 0; ready && u < active; ++u) ready = hipEventQuery(P.t1[u]) == hipSuccess;
+    if (ready) {
+        for (int u = 0; u < active; ++u) {
+            float ms = 0.f;
+            P.units[u].ms = hipEventElapsedTime(&ms, P.t0[u], P.t1[u]) == hipSuccess ? ms : 0.0;
+        }
+        P.calib = 2;
+        if (fwd_schedule_measured(P.units, P.form_items(), fLanes + 1, kFwdMaxUnits))      // else: static lanes kept, nothing published
+            g_fcalib.publish(P.key, P.units);
+    }
+    (void)hipGetLastError();   // hipEventQuery's "not ready" is not an error of this call
+}
+
+// The forms are independent grids.  Back to back on one stream each would wait for the previous one's LAST workgroup (a
+// stride-2 3x3 layer has 28 items of 144 chunks: half a millisecond of tail on an empty chip), so every form but the largest
+// goes to one of THREE side streams of the library (fork / join with events around the group; the runtime multiplexes a
+// process's streams onto four hardware queues, so more lanes would only queue up behind each other): forms are dealt to the
+// least-loaded lane, largest first, and the long items of the small forms run beside the large forms' thousands of short
+// ones, as in one grid.  Launch kFwdCalibAt of a plan also brackets every unit with the plan's timing events.
+static int fwd_launch_units(FwdPlan& P, const FwdLayerDev* dl, const FwdItemDev* items, float* parts, hipStream_t stream) {
+    ProfScope prof(kProfConvFwd, P.flops, P.bytes, stream);
+    SideStreams<fLanes>::Set& side = g_fwd_side.current();
+    const int active = (int)P.units.size();
+    const bool fork = active > 1 && side.ok;
+    const bool measure = fork && P.calib == 0 && P.launches == kFwdCalibAt && active <= kFwdMaxUnits && P.timing_events();
+    if (fork) PLEAS_HIP_CHECK(hipEventRecord(side.forked, stream));
+    bool lane_used[fLanes + 1] = {false};
+    for (int o = 0; o < active; ++o) {
+        const FwdUnit& un = P.units[o];
+        const int lane = fork ? un.lane : 0;          // lane 0 = the caller's stream
+        hipStream_t st = lane == 0 ? stream : side.streams[lane - 1];
+        if (lane > 0 && !lane_used[lane]) PLEAS_HIP_CHECK(hipStreamWaitEvent(st, side.forked, 0));
+        lane_used[lane] = true;
+        if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t0[o], st));
+        hipLaunchKernelGGL(kFwdKernels[un.form].batch[P.split ? 1 : 0], dim3((unsigned)un.count), dim3(fThreads), P.form_lds[un.form], st,
+                           dl, items + un.begin, parts);
+        if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t1[o], st));
+    }
+    if (measure) P.calib = 1;
+    for (int lane = 1; lane <= fLanes; ++lane)
+        if (lane_used[lane]) {
+            PLEAS_HIP_CHECK(hipEventRecord(side.joined[lane - 1], side.streams[lane - 1]));
+            PLEAS_HIP_CHECK(hipStreamWaitEvent(stream, side.joined[lane - 1], 0));
+        }
+    return PLEAS_OK;
 }
 
 extern "C" int pleas_fwd_batch(const pleas_fwd_layer* layers, int n_layers, float* loss, void* ws, size_t ws_bytes,
@@ -1559,14 +1330,11 @@ extern "C" int pleas_fwd_batch(const pleas_fwd_layer* layers, int n_layers, floa
         hit->key.swap(key);
     }
     FwdPlan& P = *hit;
-    if (P.calib == 0 && P.launches == 0) {      // a new plan: start from what another fitter measured on this geometry
-        const std::vector<int64_t> geo = fwd_geometry_key(P.key);
-        for (const auto& kv : g_fcalib)
-            if (kv.first == geo) {
-                P.units = kv.second;
-                P.calib = 2;
-            }
-    }
+    if (P.calib == 0 && P.launches == 0)        // a new plan: start from what another fitter measured on this geometry
+        if (const std::vector<FwdUnit>* measured = g_fcalib.find(P.key)) {
+            P.units = *measured;
+            P.calib = 2;
+        }
     if (ws_fresh) P.uploaded = false;
     if (!ws || ws_bytes < P.total) {
         std::snprintf(g_last_error, sizeof(g_last_error), "conv_fwd workspace too small: need %zu bytes", P.total);
@@ -1599,73 +1367,10 @@ extern "C" int pleas_fwd_batch(const pleas_fwd_layer* layers, int n_layers, floa
         PLEAS_LAUNCH_CHECK("fwd_set_ptrs_kernel");
     }
     float* parts = reinterpret_cast<float*>(base + P.off_parts);
-    {
-        // The forms are independent grids.  Back to back on one stream each would wait for the previous one's LAST
-        // workgroup (a stride-2 3x3 layer has 28 items of 144 chunks: half a millisecond of tail on an empty chip), so every
-        // form but the largest goes to one of THREE side streams of the library (fork / join with events around the group;
-        // the runtime multiplexes a process's streams onto four hardware queues, so more lanes would only queue up behind
-        // each other): forms are dealt to the least-loaded lane, largest first, and the long items of the small forms run
-        // beside the large forms' thousands of short ones, as in one grid.
-        ProfScope prof(kProfConvFwd, P.flops, P.bytes, stream);
-        const FwdItemDev* items = reinterpret_cast<const FwdItemDev*>(base + P.off_items);
-        FwdSideStreams& side = fwd_side_streams();
-        static const bool serial = std::getenv("PLEAS_FWD_SERIAL") && std::atoi(std::getenv("PLEAS_FWD_SERIAL")) != 0;
-        const int active = (int)P.units.size();
-        const bool fork = !serial && active > 1 && side.ok;
-        static const bool calibrate = !(std::getenv("PLEAS_FWD_CALIBRATE") && std::atoi(std::getenv("PLEAS_FWD_CALIBRATE")) == 0);
-        ++P.launches;
-        if (P.calib == 1) {          // the calibration launch's events: all complete?  then cut long units and deal the lanes
-            bool ready = true;
-            for (int u = 0; ready && u < active; ++u) ready = hipEventQuery(P.t1[u]) == hipSuccess;
-            if (ready) {
-                for (int u = 0; u < active; ++u) {
-                    float ms = 0.f;
-                    P.units[u].ms = hipEventElapsedTime(&ms, P.t0[u], P.t1[u]) == hipSuccess ? ms : 0.0;
-                }
-                P.calib = 2;
-                if (fwd_schedule_measured(P)) {      // else: static lanes kept, nothing published to other fitters
-                    if (g_fcalib.size() >= 16) g_fcalib.erase(g_fcalib.begin());
-                    g_fcalib.emplace_back(fwd_geometry_key(P.key), P.units);
-                }
-            }
-            (void)hipGetLastError();   // hipEventQuery's "not ready" is not an error of this call
-        }
-        const bool measure = fork && calibrate && P.calib == 0 && P.launches == kCalibAt && active <= fMaxUnits && P.timing_events();
-        if (fork) PLEAS_HIP_CHECK(hipEventRecord(side.forked, stream));
-        bool lane_used[fLanes + 1] = {false};
-        for (size_t o = 0; o < P.units.size(); ++o) {
-            const FwdPlan::Unit& un = P.units[o];
-            const int f = un.form;
-            const int lane = fork ? un.lane : 0;          // lane 0 = the caller's stream
-            hipStream_t st = lane == 0 ? stream : side.streams[lane - 1];
-            if (lane > 0 && !lane_used[lane]) PLEAS_HIP_CHECK(hipStreamWaitEvent(st, side.forked, 0));
-            lane_used[lane] = true;
-            const dim3 grid((unsigned)un.count);
-            const FwdItemDev* its = items + un.begin;
-            const size_t lds = P.form_lds[f];
-            if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t0[o], st));
-            if (P.split && fwd_form_splits(f)) {
-                switch (f) {
-#define PLEAS_FWD_LAUNCH(F) case F: hipLaunchKernelGGL((fwd_batch_kernel<F, 1>), grid, dim3(fThreads), lds, st, dl, its, parts); break
-                    PLEAS_FWD_LAUNCH(4); PLEAS_FWD_LAUNCH(6); PLEAS_FWD_LAUNCH(7); PLEAS_FWD_LAUNCH(9);
-#undef PLEAS_FWD_LAUNCH
-                }
-            } else
-            switch (f) {
-#define PLEAS_FWD_LAUNCH(F) case F: hipLaunchKernelGGL((fwd_batch_kernel<F, 0>), grid, dim3(fThreads), lds, st, dl, its, parts); break
-                PLEAS_FWD_LAUNCH(0); PLEAS_FWD_LAUNCH(1); PLEAS_FWD_LAUNCH(2); PLEAS_FWD_LAUNCH(3); PLEAS_FWD_LAUNCH(4);
-                PLEAS_FWD_LAUNCH(5); PLEAS_FWD_LAUNCH(6); PLEAS_FWD_LAUNCH(7); PLEAS_FWD_LAUNCH(8); PLEAS_FWD_LAUNCH(9);
-#undef PLEAS_FWD_LAUNCH
-            }
-            if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t1[o], st));
-        }
-        if (measure) P.calib = 1;
-        for (int lane = 1; lane <= fLanes; ++lane)
-            if (lane_used[lane]) {
-                PLEAS_HIP_CHECK(hipEventRecord(side.joined[lane - 1], side.streams[lane - 1]));
-                PLEAS_HIP_CHECK(hipStreamWaitEvent(stream, side.joined[lane - 1], 0));
-            }
-    }
+    ++P.launches;
+    fwd_adopt_measurements(P);
+    if (const int rc = fwd_launch_units(P, dl, reinterpret_cast<const FwdItemDev*>(base + P.off_items), parts, stream); rc != PLEAS_OK)
+        return rc;
     PLEAS_LAUNCH_CHECK("fwd_batch_kernel");
     hipLaunchKernelGGL(fwd_loss_kernel, dim3(n_layers), dim3(64), 0, stream, parts,
                        reinterpret_cast<const FwdLossDev*>(base + P.off_loss), loss);

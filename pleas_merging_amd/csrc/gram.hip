@@ -739,7 +739,6 @@ struct BatchPlan {
 static PlanCache<BatchPlan, 2> g_bplans;
 static std::mutex g_bplan_mu;
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Layout + work list for a node sequence; device pointers are filled relative to `ws` later.
 static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, float* const* group_acc, const int* group_C,
@@ -870,15 +869,15 @@ static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, floa
     P.reduce_blocks = blk;
     size_t off = 0;
     P.off_nodes = off;
-    off = align_up(off + P.nodes.size() * sizeof(GramNodeDev), 256);
+    off = align256(off + P.nodes.size() * sizeof(GramNodeDev));
     P.off_items = off;
-    off = align_up(off + P.items.size() * sizeof(GramItemDev), 256);
+    off = align256(off + P.items.size() * sizeof(GramItemDev));
     P.off_groups = off;
-    off = align_up(off + P.groups.size() * sizeof(GramGroupDev), 256);
+    off = align256(off + P.groups.size() * sizeof(GramGroupDev));
     P.off_gn = off;
-    off = align_up(off + P.group_nodes.size() * sizeof(int), 256);
+    off = align256(off + P.group_nodes.size() * sizeof(int));
     P.off_bg = off;
-    off = align_up(off + P.blk_group.size() * sizeof(int), 256);
+    off = align256(off + P.blk_group.size() * sizeof(int));
     P.off_slabs = off;
     P.slab_bytes = (double)slabs * sizeof(float);
     P.total = off + slabs * sizeof(float);

@@ -128,7 +128,6 @@ struct MergePlan {
 };
 static PlanCache<MergePlan, 1> g_mplans;
 static std::mutex g_mplan_mu;
-static size_t malign(size_t v) { return (v + 255) / 256 * 256; }
 
 static int build_merge_plan(MergePlan& P, const pleas_merge_item* it, int n) {
     P.items.assign(n, MergeItemDev());
@@ -167,8 +166,8 @@ static int build_merge_plan(MergePlan& P, const pleas_merge_item* it, int n) {
         P.bytes += 3.0 * (double)(m.outer * m.rows_out * m.inner) * sizeof(float);
     }
     P.off_items = 0;
-    P.off_blocks = malign(P.items.size() * sizeof(MergeItemDev));
-    P.total = P.off_blocks + malign(P.block_item.size() * sizeof(int));
+    P.off_blocks = align256(P.items.size() * sizeof(MergeItemDev));
+    P.total = P.off_blocks + align256(P.block_item.size() * sizeof(int));
     P.uploaded = false;
     return PLEAS_OK;
 }

@@ -504,7 +504,6 @@ struct NeqPlan {
 };
 static PlanCache<NeqPlan, 1> g_nplans;
 static std::mutex g_nplan_mu;
-static size_t nalign(size_t v) { return (v + 255) / 256 * 256; }
 
 static int build_neq_plan(NeqPlan& P, const pleas_neq_layer* ly, int n) {
     P.layers.assign(n, NeqLayerDev());
@@ -587,11 +586,11 @@ static int build_neq_plan(NeqPlan& P, const pleas_neq_layer* ly, int n) {
     P.items = xcd_order_items(work, NeqItemDev{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0}, /*by_default=*/false);
     size_t off = 0;
     P.off_layers = off;
-    off = nalign(off + P.layers.size() * sizeof(NeqLayerDev));
+    off = align256(off + P.layers.size() * sizeof(NeqLayerDev));
     P.off_items = off;
-    off = nalign(off + P.items.size() * sizeof(NeqItemDev));
+    off = align256(off + P.items.size() * sizeof(NeqItemDev));
     P.off_red = off;
-    off = nalign(off + P.red.size() * sizeof(NeqReduceDev));
+    off = align256(off + P.red.size() * sizeof(NeqReduceDev));
     P.off_slabs = off;
     P.total = off + slabs * sizeof(float);
     for (int i = 0; i < n; ++i) P.layers[i].slab = reinterpret_cast<float*>(slab_off[i]);

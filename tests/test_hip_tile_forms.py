@@ -41,7 +41,7 @@ WGRAD_EXACT_RATIO = 3.396e-07
 FWD_SPLIT_BOUND = 4 * FWD_EXACT_RATIO
 WGRAD_SPLIT_BOUND = 4 * WGRAD_EXACT_RATIO
 
-# Forms with a split-bf16 twin -- fwd_form_splits() in csrc/conv_fwd.hip, which has no query: keep the two in step.  Every other
+# Forms with a split-bf16 twin -- kFwdForms[].split in csrc/conv_fwd.hip, which has no query: keep the two in step.  Every other
 # form runs the exact kernel inside the same launch and is held to the exact bound under either arithmetic.
 SPLIT_FWD_FORMS = (4, 6, 7, 9)
 
