@@ -125,11 +125,26 @@ struct ProfScope {
 };
 
 
-// ---- a few plans per grouped launch (host side).
-// A plan (work-item tables of one layer / node list) is keyed by its geometry AND the address of the caller's workspace
-// the tables are uploaded to (element WS of the key).  Keeping several lets callers that alternate inside one process --
-// two fitters, the per-group contractions of weight matching, matching next to PLeaS -- find their plan again instead
-// of rebuilding and re-uploading it at every call.  Slots are recycled round robin.  Guarded by the caller's mutex.
+// a caller's workspace holds fewer than the `need` bytes `what` asks for: the answer a caller sizes its workspace again on
+inline int workspace_too_small(const char* what, size_t need) {
+    std::snprintf(g_last_error, sizeof(g_last_error), "%s workspace too small: need %zu bytes", what, need);
+    return PLEAS_ENOMEM;
+}
+
+// ---- a few plans per grouped launch (host side), and the ws / ws_fresh protocol of include/pleas_hip.h written once.
+// A plan (work-item tables of one layer / node list; members `key`, `total` = workspace bytes, `uploaded`) is keyed by its
+// geometry AND the address of the caller's workspace the tables are uploaded to (element WS of the key).  Keeping several lets
+// callers that alternate inside one process -- two fitters, the per-group contractions of weight matching, matching next to
+// PLeaS -- find their plan again instead of rebuilding and re-uploading it at every call.  Slots are recycled round robin.
+// Guarded by the caller's mutex.  A launch entry point calls `get`, then `prepare`, then launches.
+struct PlanTable {              // one static table of a plan: `bytes` from `host` to `offset` of the workspace
+    size_t offset;
+    const void* host;
+    size_t bytes;
+};
+template <class T>
+inline PlanTable plan_table(size_t offset, const std::vector<T>& v) { return PlanTable{offset, v.data(), v.size() * sizeof(T)}; }
+
 template <class Plan, int WS, int N = 8>
 struct PlanCache {
     Plan slots[N];
@@ -150,6 +165,37 @@ struct PlanCache {
     void claims_workspace(const Plan& p) {
         for (auto& o : slots)
             if (&o != &p && (int)o.key.size() > WS && (int)p.key.size() > WS && o.key[WS] == p.key[WS]) o.uploaded = false;
+    }
+    // The plan of `key` into `plan`: the cached one, or a recycled slot filled by `build(Plan&)`, whose error code is passed on
+    // (the slot then stays without a key).  `key` is consumed.
+    template <class Build>
+    int get(std::vector<int64_t>& key, Plan*& plan, Build&& build) {
+        if ((plan = find(key))) return PLEAS_OK;
+        Plan& p = take();
+        const int rc = build(p);
+        if (rc != PLEAS_OK) return rc;
+        p.key.swap(key);
+        plan = &p;
+        return PLEAS_OK;
+    }
+    // p's static tables into the caller's workspace, once per (plan, workspace).  `ws_fresh`: the caller says the tables inside
+    // ws are not (or no longer) there.  A workspace below p.total drops the plan's key (the caller comes back with another
+    // workspace, i.e. another key) and answers PLEAS_ENOMEM.  `tables()` lists what to upload and is called only when an upload
+    // is due; what it points at must live until this returns (the stream is synchronised: once per plan).
+    template <class Tables>
+    int prepare(Plan& p, const char* what, void* ws, size_t ws_bytes, int ws_fresh, hipStream_t stream, Tables&& tables) {
+        if (ws_fresh) p.uploaded = false;
+        if (!ws || ws_bytes < p.total) {
+            p.key.clear();
+            return workspace_too_small(what, p.total);
+        }
+        if (p.uploaded) return PLEAS_OK;
+        claims_workspace(p);
+        for (const PlanTable& t : tables())
+            if (t.bytes) PLEAS_HIP_CHECK(hipMemcpyAsync((char*)ws + t.offset, t.host, t.bytes, hipMemcpyHostToDevice, stream));
+        PLEAS_HIP_CHECK(hipStreamSynchronize(stream));
+        p.uploaded = true;
+        return PLEAS_OK;
     }
 };
 

@@ -799,39 +799,22 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
     hipStream_t stream = (hipStream_t)stream_;
     std::lock_guard<std::mutex> lk(g_wplan_mu);
     std::vector<int64_t> key = wgrad_key(layers, n_layers, ws);
-    WgradPlan* hit = g_wgrad_plans.find(key);
-    if (!hit) {
-        hit = &g_wgrad_plans.take();
-        const int rc = build_wgrad_plan(*hit, layers, n_layers);
-        if (rc != PLEAS_OK) return rc;
-        hit->key.swap(key);
-    }
+    WgradPlan* hit = nullptr;
+    if (const int rc = g_wgrad_plans.get(key, hit, [&](WgradPlan& p) { return build_wgrad_plan(p, layers, n_layers); }); rc != PLEAS_OK)
+        return rc;
     WgradPlan& P = *hit;
-    if (ws_fresh) P.uploaded = false;  // caller says the tables inside ws are not (or no longer) there
-    if (!ws || ws_bytes < P.total) {
-        std::snprintf(g_last_error, sizeof(g_last_error), "wgrad workspace too small: need %zu bytes", P.total);
-        P.key.clear();
-        return PLEAS_ENOMEM;
-    }
     char* base = (char*)ws;
-    if (!P.uploaded) {
-        g_wgrad_plans.claims_workspace(P);
-        float* slab0 = reinterpret_cast<float*>(base + P.off_slabs);
-        std::vector<WgradLayerDev> abs_layers = P.layers;
-        for (auto& d : abs_layers) d.slab = slab0 + reinterpret_cast<size_t>(d.slab);
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_layers, abs_layers.data(), abs_layers.size() * sizeof(WgradLayerDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_items, P.items.data(), P.items.size() * sizeof(WgradItemDev),
-                                       hipMemcpyHostToDevice, stream));
-        if (!P.blk_layer.empty()) {
-            PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_bl, P.blk_layer.data(), P.blk_layer.size() * sizeof(int),
-                                           hipMemcpyHostToDevice, stream));
-            PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_bb, P.blk_begin.data(), P.blk_begin.size() * sizeof(int),
-                                           hipMemcpyHostToDevice, stream));
-        }
-        PLEAS_HIP_CHECK(hipStreamSynchronize(stream));
-        P.uploaded = true;
-    }
+    std::vector<WgradLayerDev> abs_layers;      // the layers with their slab offsets made pointers into THIS workspace
+    if (const int rc = g_wgrad_plans.prepare(P, "wgrad", ws, ws_bytes, ws_fresh, stream, [&] {
+            float* slab0 = reinterpret_cast<float*>(base + P.off_slabs);
+            abs_layers = P.layers;
+            for (auto& d : abs_layers) d.slab = slab0 + reinterpret_cast<size_t>(d.slab);
+            // the reduce pass's two tables are empty (and skipped) when no layer is cut along K
+            return std::vector<PlanTable>{plan_table(P.off_layers, abs_layers), plan_table(P.off_items, P.items),
+                                          plan_table(P.off_bl, P.blk_layer), plan_table(P.off_bb, P.blk_begin)};
+        });
+        rc != PLEAS_OK)
+        return rc;
     WgradLayerDev* dl = reinterpret_cast<WgradLayerDev*>(base + P.off_layers);
     for (int b0 = 0; b0 < n_layers; b0 += cPtrBatch) {
         WgradPtrBatch pb;

@@ -1322,37 +1322,22 @@ extern "C" int pleas_fwd_batch(const pleas_fwd_layer* layers, int n_layers, floa
         key.push_back(bits[0]);
         key.push_back(bits[1]);
     }
-    FwdPlan* hit = g_fplans.find(key);
-    if (!hit) {
-        hit = &g_fplans.take();
-        const int rc = build_fwd_plan(*hit, layers, n_layers);
-        if (rc != PLEAS_OK) return rc;
-        hit->key.swap(key);
-    }
+    FwdPlan* hit = nullptr;
+    if (const int rc = g_fplans.get(key, hit, [&](FwdPlan& p) { return build_fwd_plan(p, layers, n_layers); }); rc != PLEAS_OK)
+        return rc;
     FwdPlan& P = *hit;
     if (P.calib == 0 && P.launches == 0)        // a new plan: start from what another fitter measured on this geometry
         if (const std::vector<FwdUnit>* measured = g_fcalib.find(P.key)) {
             P.units = *measured;
             P.calib = 2;
         }
-    if (ws_fresh) P.uploaded = false;
-    if (!ws || ws_bytes < P.total) {
-        std::snprintf(g_last_error, sizeof(g_last_error), "conv_fwd workspace too small: need %zu bytes", P.total);
-        P.key.clear();
-        return PLEAS_ENOMEM;
-    }
+    if (const int rc = g_fplans.prepare(P, "conv_fwd", ws, ws_bytes, ws_fresh, stream, [&] {
+            return std::vector<PlanTable>{plan_table(P.off_layers, P.layers), plan_table(P.off_items, P.items),
+                                          plan_table(P.off_loss, P.loss)};
+        });
+        rc != PLEAS_OK)
+        return rc;
     char* base = (char*)ws;
-    if (!P.uploaded) {
-        g_fplans.claims_workspace(P);
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_layers, P.layers.data(), P.layers.size() * sizeof(FwdLayerDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_items, P.items.data(), P.items.size() * sizeof(FwdItemDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_loss, P.loss.data(), P.loss.size() * sizeof(FwdLossDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipStreamSynchronize(stream));
-        P.uploaded = true;
-    }
     FwdLayerDev* dl = reinterpret_cast<FwdLayerDev*>(base + P.off_layers);
     for (int b0 = 0; b0 < n_layers; b0 += fPtrBatch) {
         FwdPtrBatch pb;

@@ -665,10 +665,7 @@ extern "C" int pleas_gram_accum(const float* x, const float* y, int B, int C, in
     if (epilogue != PLEAS_EPI_INNER && epilogue != PLEAS_EPI_NEG_CDIST) return bad_arg("epilogue");
     const bool aligned = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
     const GramPlan p = make_plan(B, C, HW, aligned);
-    if (!ws || ws_bytes < p.ws_bytes) {
-        std::snprintf(g_last_error, sizeof(g_last_error), "gram workspace too small: need %zu bytes", p.ws_bytes);
-        return PLEAS_ENOMEM;
-    }
+    if (!ws || ws_bytes < p.ws_bytes) return workspace_too_small("gram", p.ws_bytes);
     hipStream_t stream = (hipStream_t)stream_;
     GramGeom g;
     g.x = x;
@@ -946,43 +943,27 @@ extern "C" int pleas_gram_batch(const pleas_gram_node* nodes, int n_nodes, float
     hipStream_t stream = (hipStream_t)stream_;
     std::lock_guard<std::mutex> lk(g_bplan_mu);
     std::vector<int64_t> key = batch_key(nodes, n_nodes, group_acc, group_C, n_groups, ws);
-    BatchPlan* hit = g_bplans.find(key);
-    if (!hit) {
-        hit = &g_bplans.take();
-        const int rc = build_batch_plan(*hit, nodes, n_nodes, group_acc, group_C, n_groups);
-        if (rc != PLEAS_OK) return rc;
-        hit->key.swap(key);
-    }
+    BatchPlan* hit = nullptr;
+    if (const int rc = g_bplans.get(key, hit, [&](BatchPlan& p) { return build_batch_plan(p, nodes, n_nodes, group_acc, group_C, n_groups); });
+        rc != PLEAS_OK)
+        return rc;
     BatchPlan& P = *hit;
-    if (ws_fresh) P.uploaded = false;  // caller says the tables inside ws are not (or no longer) there
-    if (!ws || ws_bytes < P.total) {
-        std::snprintf(g_last_error, sizeof(g_last_error), "gram_batch workspace too small: need %zu bytes", P.total);
-        P.key.clear();
-        return PLEAS_ENOMEM;
-    }
     char* base = (char*)ws;
-    if (!P.uploaded) {  // static tables: once per (shape sequence, workspace, group matrices)
-        g_bplans.claims_workspace(P);
-        float* slab0 = reinterpret_cast<float*>(base + P.off_slabs);
-        std::vector<GramNodeDev> abs_nodes = P.nodes;
-        for (auto& d : abs_nodes) {
-            d.gpart = slab0 + reinterpret_cast<size_t>(d.gpart);
-            d.npart = slab0 + reinterpret_cast<size_t>(d.npart);
-            d.spart = slab0 + reinterpret_cast<size_t>(d.spart);
-        }
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_nodes, abs_nodes.data(), abs_nodes.size() * sizeof(GramNodeDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_items, P.items.data(), P.items.size() * sizeof(GramItemDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_groups, P.groups.data(), P.groups.size() * sizeof(GramGroupDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_gn, P.group_nodes.data(), P.group_nodes.size() * sizeof(int),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_bg, P.blk_group.data(), P.blk_group.size() * sizeof(int),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipStreamSynchronize(stream));  // host vectors may now change; happens once per plan
-        P.uploaded = true;
-    }
+    std::vector<GramNodeDev> abs_nodes;      // the nodes with their slab offsets made pointers into THIS workspace
+    if (const int rc = g_bplans.prepare(P, "gram_batch", ws, ws_bytes, ws_fresh, stream, [&] {
+            float* slab0 = reinterpret_cast<float*>(base + P.off_slabs);
+            abs_nodes = P.nodes;
+            for (auto& d : abs_nodes) {
+                d.gpart = slab0 + reinterpret_cast<size_t>(d.gpart);
+                d.npart = slab0 + reinterpret_cast<size_t>(d.npart);
+                d.spart = slab0 + reinterpret_cast<size_t>(d.spart);
+            }
+            return std::vector<PlanTable>{plan_table(P.off_nodes, abs_nodes), plan_table(P.off_items, P.items),
+                                          plan_table(P.off_groups, P.groups), plan_table(P.off_gn, P.group_nodes),
+                                          plan_table(P.off_bg, P.blk_group)};
+        });
+        rc != PLEAS_OK)
+        return rc;
     GramNodeDev* dnodes = reinterpret_cast<GramNodeDev*>(base + P.off_nodes);
     for (int b0 = 0; b0 < n_nodes; b0 += kPtrBatch) {
         GramPtrBatch pb;

@@ -203,31 +203,17 @@ extern "C" int pleas_merge_batch(const pleas_merge_item* items, int n_items, voi
                           (int64_t)m.sub_h, (int64_t)m.sub_w})
             key.push_back(v);
     }
-    MergePlan* hit = g_mplans.find(key);
-    if (!hit) {
-        hit = &g_mplans.take();
-        const int rc = build_merge_plan(*hit, items, n_items);
-        if (rc != PLEAS_OK) return rc;
-        hit->key.swap(key);
-    }
+    MergePlan* hit = nullptr;
+    if (const int rc = g_mplans.get(key, hit, [&](MergePlan& p) { return build_merge_plan(p, items, n_items); }); rc != PLEAS_OK)
+        return rc;
     MergePlan& P = *hit;
-    if (ws_fresh) P.uploaded = false;
-    if (P.block_item.empty()) return PLEAS_OK;
-    if (!ws || ws_bytes < P.total) {
-        std::snprintf(g_last_error, sizeof(g_last_error), "merge_batch workspace too small: need %zu bytes", P.total);
-        P.key.clear();
-        return PLEAS_ENOMEM;
-    }
+    if (P.block_item.empty()) return PLEAS_OK;      // nothing to write, whatever the workspace
+    if (const int rc = g_mplans.prepare(P, "merge_batch", ws, ws_bytes, ws_fresh, stream, [&] {
+            return std::vector<PlanTable>{plan_table(P.off_items, P.items), plan_table(P.off_blocks, P.block_item)};
+        });
+        rc != PLEAS_OK)
+        return rc;
     char* base = (char*)ws;
-    if (!P.uploaded) {
-        g_mplans.claims_workspace(P);
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_items, P.items.data(), P.items.size() * sizeof(MergeItemDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_blocks, P.block_item.data(), P.block_item.size() * sizeof(int),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipStreamSynchronize(stream));
-        P.uploaded = true;
-    }
     MergeItemDev* di = reinterpret_cast<MergeItemDev*>(base + P.off_items);
     for (int b0 = 0; b0 < n_items; b0 += mPtrBatch) {
         MergePtrBatch pb;

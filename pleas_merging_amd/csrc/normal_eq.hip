@@ -664,36 +664,21 @@ extern "C" int pleas_normal_eq_accum(const pleas_neq_layer* layers, int n_layers
         for (int v : {layers[i].N, layers[i].Cin, layers[i].Hin, layers[i].Win, layers[i].KH, layers[i].KW, layers[i].stride,
                       layers[i].pad})
             key.push_back(v);
-    NeqPlan* hit = g_nplans.find(key);
-    if (!hit) {
-        hit = &g_nplans.take();
-        const int rc = build_neq_plan(*hit, layers, n_layers);
-        if (rc != PLEAS_OK) return rc;
-        hit->key.swap(key);
-    }
+    NeqPlan* hit = nullptr;
+    if (const int rc = g_nplans.get(key, hit, [&](NeqPlan& p) { return build_neq_plan(p, layers, n_layers); }); rc != PLEAS_OK)
+        return rc;
     NeqPlan& P = *hit;
-    if (ws_fresh) P.uploaded = false;
-    if (!ws || ws_bytes < P.total) {
-        std::snprintf(g_last_error, sizeof(g_last_error), "normal_eq workspace too small: need %zu bytes", P.total);
-        P.key.clear();
-        return PLEAS_ENOMEM;
-    }
     char* base = (char*)ws;
-    if (!P.uploaded) {
-        g_nplans.claims_workspace(P);
-        float* slab0 = reinterpret_cast<float*>(base + P.off_slabs);
-        std::vector<NeqLayerDev> abs_layers = P.layers;
-        for (auto& d : abs_layers) d.slab = slab0 + reinterpret_cast<size_t>(d.slab);
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_layers, abs_layers.data(), abs_layers.size() * sizeof(NeqLayerDev),
-                                       hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_items, P.items.data(), P.items.size() * sizeof(NeqItemDev),
-                                       hipMemcpyHostToDevice, stream));
-        if (!P.red.empty())
-            PLEAS_HIP_CHECK(hipMemcpyAsync(base + P.off_red, P.red.data(), P.red.size() * sizeof(NeqReduceDev),
-                                           hipMemcpyHostToDevice, stream));
-        PLEAS_HIP_CHECK(hipStreamSynchronize(stream));
-        P.uploaded = true;
-    }
+    std::vector<NeqLayerDev> abs_layers;      // the layers with their slab offsets made pointers into THIS workspace
+    if (const int rc = g_nplans.prepare(P, "normal_eq", ws, ws_bytes, ws_fresh, stream, [&] {
+            float* slab0 = reinterpret_cast<float*>(base + P.off_slabs);
+            abs_layers = P.layers;
+            for (auto& d : abs_layers) d.slab = slab0 + reinterpret_cast<size_t>(d.slab);
+            return std::vector<PlanTable>{plan_table(P.off_layers, abs_layers), plan_table(P.off_items, P.items),
+                                          plan_table(P.off_red, P.red)};
+        });
+        rc != PLEAS_OK)
+        return rc;
     NeqLayerDev* dl = reinterpret_cast<NeqLayerDev*>(base + P.off_layers);
     for (int b0 = 0; b0 < n_layers; b0 += nPtrBatch) {
         NeqPtrBatch pb;

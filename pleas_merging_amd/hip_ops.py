@@ -11,6 +11,7 @@ import math
 import threading
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -145,6 +146,96 @@ def _as_bchw(t: torch.Tensor, axis: int) -> Tuple[int, int, int]:
     return math.prod(shape[:axis]), shape[axis], math.prod(shape[axis + 1:])
 
 
+class _GroupedLaunch:
+    """The protocol every grouped launch of the library follows (include/pleas_hip.h), written once: entries are queued by the
+    subclass's ``add`` (``_queue``), ``flush`` fills the struct array, sizes a DEDICATED workspace once (the plan's tables live in
+    it), launches with the ``ws_fresh`` flag, and sizes the workspace again -- once -- when the library answers
+    ``PLEAS_ENOMEM`` because the list now needs more.  ``table`` / ``relaunch`` are the per-update fast path of ``PleasFitter``.
+
+    A subclass states its ctypes struct, the names of its ``*_ws_bytes`` and launch functions, how one entry fills one struct
+    row (``_fill``), and the arguments its two calls take beside the protocol's own (``_ws_args`` / ``_launch_args``)."""
+
+    STRUCT = None
+    WS_BYTES = LAUNCH = ""
+    ENOMEM = -12                   # PLEAS_ENOMEM
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self._keep: list = []      # per pending entry: the tensors its row points at (kept alive until the launch is queued)
+        self._geo: list = []       # per pending entry: everything else of its row
+        self._arr = None
+        self._ws = None
+        self._fresh = 1
+
+    def _queue(self, tensors: tuple, geo: tuple) -> int:
+        self._keep.append(tensors)
+        self._geo.append(geo)
+        return len(self._keep) - 1
+
+    def _fill(self, row, tensors: tuple, geo: tuple) -> None:
+        raise NotImplementedError
+
+    def _ws_args(self) -> tuple:
+        return ()
+
+    def _launch_args(self, *args) -> tuple:
+        return ()
+
+    def pending(self) -> int:
+        """Entries added since the last ``flush`` / ``drop``."""
+        return len(self._keep)
+
+    def drop(self) -> None:
+        self._keep.clear()
+        self._geo.clear()
+
+    def _launch(self, fresh: int, extra: tuple) -> int:
+        return getattr(_lib.lib(), self.LAUNCH)(self._arr, len(self._arr), *extra, self._ws.data_ptr(), self._ws.numel(), fresh,
+                                                _stream())
+
+    def _flush(self, *args, keep: bool = False) -> None:
+        n = len(self._keep)
+        if n == 0:
+            return
+        if self._arr is None or len(self._arr) != n:
+            self._arr = (self.STRUCT * n)()
+        for row, tensors, geo in zip(self._arr, self._keep, self._geo):
+            self._fill(row, tensors, geo)
+        extra = self._launch_args(*args)
+        rc = self.ENOMEM
+        for _ in range(2):         # the second round: the list changed shape and needs more than the workspace holds
+            if self._ws is None:
+                lib = _lib.lib()
+                need = int(getattr(lib, self.WS_BYTES)(self._arr, n, *self._ws_args()))
+                if need == 0:
+                    raise PleasHipError("%s rejected the list: %s" % (self.WS_BYTES, lib.pleas_last_error().decode()))
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                self._fresh = 1
+            rc = self._launch(self._fresh, extra)
+            self._fresh = 0
+            if rc != self.ENOMEM:
+                break
+            self._ws = None
+        check(rc, self.LAUNCH)
+        if not keep:
+            self.drop()
+
+    def flush(self) -> None:
+        """ONE grouped launch over everything added since the last flush."""
+        self._flush()
+
+    def table(self):
+        """numpy view of the struct array of the latest ``flush`` (shares its memory): pointer fields may be rewritten before
+        ``relaunch`` -- the per-update fast path of ``PleasFitter``, which keeps every other field as it is."""
+        return None if self._arr is None else np.frombuffer(self._arr, dtype=np.dtype(self.STRUCT))
+
+    def relaunch(self, *args) -> None:
+        """The launch of the latest ``flush`` again, with the table as it is now."""
+        if self._keep or self._arr is None or self._ws is None:
+            raise PleasHipError("%s.relaunch: nothing flushed yet, or entries pending" % type(self).__name__)
+        check(self._launch(0, self._launch_args(*args)), self.LAUNCH)
+
+
 # ---------------------------------------------------------------------------------------- gram / cdist
 def gram_ws_bytes(B: int, C: int, HW: int) -> int:
     return int(_lib.lib().pleas_gram_ws_bytes(B, C, HW))
@@ -183,7 +274,7 @@ def cross_features_inner_product(x: torch.Tensor, y: torch.Tensor, a: int) -> to
     return gram_accum(x, y, a, out, EPI_INNER, accumulate=False)
 
 
-class GramBatch:
+class GramBatch(_GroupedLaunch):
     """Collects the tracked nodes of one forward pass and contracts them all in ONE grouped launch
     (``pleas_gram_batch``): ``add`` while the models run, ``flush`` once per batch.
 
@@ -191,94 +282,66 @@ class GramBatch:
     out of place); they are released right after the launch is queued.
     """
 
+    STRUCT, WS_BYTES, LAUNCH = _lib.GramNode, "pleas_gram_batch_ws_bytes", "pleas_gram_batch"
+
     def __init__(self, group_mats: Sequence[torch.Tensor], epilogue: int):
         _need_gpu(*group_mats)
+        super().__init__(group_mats[0].device)
         self.mats = list(group_mats)
         self.epilogue = epilogue
         k = len(self.mats)
         self._acc = (ctypes.c_void_p * k)(*[m.data_ptr() for m in self.mats])
         self._gc = (ctypes.c_int * k)(*[m.shape[0] for m in self.mats])
-        self._keep: list = []
-        self._meta: list = []
-        self._arr = None
-        self._ws = None
-        self.device = self.mats[0].device
 
     def add(self, x: torch.Tensor, y: torch.Tensor, axis: int, group: int) -> int:
         """Queue one contracted node; returns its index in this batch (the handle ``add_derived`` refers to)."""
         if x.shape != y.shape or not x.is_cuda or x.dtype != torch.float32 or y.dtype != torch.float32:
             raise PleasHipError("GramBatch.add: fp32 CUDA operands of equal shape expected")
         x, y = x.contiguous(), y.contiguous()
-        self._keep.append((x, y))
-        self._meta.append(_as_bchw(x, axis) + (group, None))
-        return len(self._keep) - 1
+        return self._queue((x, y), _as_bchw(x, axis) + (group, None))
 
     def add_derived(self, source: int, scale_x: torch.Tensor, shift_x: torch.Tensor, scale_y: torch.Tensor,
                     shift_y: torch.Tensor, group: int) -> int:
         """Queue a node whose operands are per-channel affine images ``scale * v + shift`` of node ``source``'s operands
         (an eval-mode BatchNorm of a tracked convolution): no contraction, the reduce pass derives its contribution."""
-        if not 0 <= source < len(self._keep) or self._meta[source][4] is not None:
+        if not 0 <= source < len(self._keep) or self._geo[source][4] is not None:
             raise PleasHipError("GramBatch.add_derived: source must be a contracted node of this batch")
-        B, C, HW = self._meta[source][:3]
+        B, C, HW = self._geo[source][:3]
         for t in (scale_x, shift_x, scale_y, shift_y):
             if not t.is_cuda or t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous():
                 raise PleasHipError("GramBatch.add_derived: scale / shift must be contiguous fp32 CUDA vectors of length C")
-        self._keep.append((scale_x, shift_x, scale_y, shift_y))
-        self._meta.append((B, C, HW, group, source))
-        return len(self._keep) - 1
+        return self._queue((scale_x, shift_x, scale_y, shift_y), (B, C, HW, group, source))
+
+    def _fill(self, a, t, geo) -> None:
+        a.B, a.C, a.HW, a.group, src = geo
+        if src is None:
+            a.x, a.y, a.derived, a.source = t[0].data_ptr(), t[1].data_ptr(), 0, 0
+            a.scale_x = a.shift_x = a.scale_y = a.shift_y = None
+        else:
+            a.x = a.y = None
+            a.derived, a.source = 1, src
+            a.scale_x, a.shift_x, a.scale_y, a.shift_y = (v.data_ptr() for v in t)
+
+    def _ws_args(self) -> tuple:
+        return self._gc, len(self.mats)
+
+    def _launch_args(self, accumulate: bool = True) -> tuple:
+        return self._acc, self._gc, len(self.mats), self.epilogue, int(bool(accumulate))
 
     def flush(self, accumulate: bool = True, keep: bool = False) -> None:
         """Contract everything added since the last flush.  ``keep=True`` leaves the node list in place (a caller that
         contracts the same device tensors again)."""
-        n = len(self._keep)
-        if n == 0:
-            return
-        if self._arr is None or len(self._arr) != n:
-            self._arr = (_lib.GramNode * n)()
-        arr = self._arr
-        for i, (t, (B, C, HW, g, src)) in enumerate(zip(self._keep, self._meta)):
-            a = arr[i]
-            a.B, a.C, a.HW, a.group = B, C, HW, g
-            if src is None:
-                a.x, a.y, a.derived, a.source = t[0].data_ptr(), t[1].data_ptr(), 0, 0
-                a.scale_x = a.shift_x = a.scale_y = a.shift_y = None
-            else:
-                a.x = a.y = None
-                a.derived, a.source = 1, src
-                a.scale_x, a.shift_x, a.scale_y, a.shift_y = (v.data_ptr() for v in t)
-        lib = _lib.lib()
-        if self._ws is None:
-            need = int(lib.pleas_gram_batch_ws_bytes(arr, n, self._gc, len(self.mats)))
-            if need == 0:
-                raise PleasHipError("pleas_gram_batch_ws_bytes rejected the node list: %s" % lib.pleas_last_error().decode())
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)  # dedicated: tables live in it
-            self._fresh = 1
-        rc = lib.pleas_gram_batch(arr, n, self._acc, self._gc, len(self.mats), self.epilogue, int(bool(accumulate)),
-                                  self._ws.data_ptr(), self._ws.numel(), self._fresh, _stream())
-        self._fresh = 0
-        if rc == -12:  # node list changed shape: size the workspace again
-            self._ws = None
-            self.flush(accumulate, keep)
-            return
-        check(rc, "pleas_gram_batch")
-        if not keep:
-            self._keep.clear()
-            self._meta.clear()
-
-    def drop(self) -> None:
-        self._keep.clear()
-        self._meta.clear()
+        self._flush(accumulate, keep=keep)
 
 
 # ---------------------------------------------------------------------------------------- LAP
-def solve_lsa_batched(costs: Sequence[torch.Tensor], maximize: bool = True) -> List[torch.Tensor]:
-    """All assignment problems of a model pair in one launch; returns device int64 vectors."""
-    if not costs:
-        return []
+def _square_costs(costs: Sequence[torch.Tensor], min_n: int):
+    """A list of square device cost matrices as the batched solvers take it: ``(mats, outs, cost_ptrs, out_ptrs, ns)`` with
+    ``mats`` kept alive by the caller, ``outs`` the int64 result vectors."""
     _need_gpu(*costs)
     mats = []
     for c in costs:
-        if c.dim() != 2 or c.shape[0] != c.shape[1]:
+        if c.dim() != 2 or c.shape[0] != c.shape[1] or c.shape[0] < min_n:
             raise PleasHipError("square cost matrices expected, got %s" % (tuple(c.shape),))
         if c.shape[0] > _lib.LSAP_MAX_N:
             raise PleasHipError("n = %d exceeds PLEAS_LSAP_MAX_N = %d" % (c.shape[0], _lib.LSAP_MAX_N))
@@ -288,7 +351,26 @@ def solve_lsa_batched(costs: Sequence[torch.Tensor], maximize: bool = True) -> L
     cost_ptrs = (ctypes.c_void_p * k)(*[m.data_ptr() for m in mats])
     out_ptrs = (ctypes.c_void_p * k)(*[o.data_ptr() for o in outs])
     ns = (ctypes.c_int * k)(*[m.shape[0] for m in mats])
-    rc = _lib.lib().pleas_lsap_batched(cost_ptrs, ns, k, int(bool(maximize)), out_ptrs, _stream())
+    return mats, outs, cost_ptrs, out_ptrs, ns
+
+
+def _host_cost(A: torch.Tensor, name: str, device_name: str):
+    """A square host cost matrix as the host solvers take it (fp32 / fp64, contiguous) and its int64 result vector."""
+    if A.is_cuda:
+        raise PleasHipError("%s takes a CPU tensor; use %s for device tensors" % (name, device_name))
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
+        raise PleasHipError("square cost matrix expected, got %s" % (tuple(A.shape),))
+    if A.dtype not in (torch.float32, torch.float64):
+        A = A.double()
+    return A.contiguous(), torch.empty(A.shape[0], dtype=torch.int64)
+
+
+def solve_lsa_batched(costs: Sequence[torch.Tensor], maximize: bool = True) -> List[torch.Tensor]:
+    """All assignment problems of a model pair in one launch; returns device int64 vectors."""
+    if not costs:
+        return []
+    mats, outs, cost_ptrs, out_ptrs, ns = _square_costs(costs, 0)
+    rc = _lib.lib().pleas_lsap_batched(cost_ptrs, ns, len(mats), int(bool(maximize)), out_ptrs, _stream())
     check(rc, "pleas_lsap_batched")
     return outs
 
@@ -302,14 +384,7 @@ def host_solve_lsa(A: torch.Tensor, maximize: bool = True) -> torch.Tensor:
     """``pleas_lsap_host``: the library's solver on a HOST cost matrix (fp32 / fp64 CPU tensor), synchronous; same
     ``col_ind`` as scipy.  For callers that keep their data on the host (weight matching of CPU state dicts); device
     tensors belong to ``hip_solve_lsa`` and are refused here -- nothing falls back from one to the other."""
-    if A.is_cuda:
-        raise PleasHipError("host_solve_lsa takes a CPU tensor; use hip_solve_lsa for device tensors")
-    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
-        raise PleasHipError("square cost matrix expected, got %s" % (tuple(A.shape),))
-    if A.dtype not in (torch.float32, torch.float64):
-        A = A.double()
-    A = A.contiguous()
-    out = torch.empty(A.shape[0], dtype=torch.int64)
+    A, out = _host_cost(A, "host_solve_lsa", "hip_solve_lsa")
     check(_lib.lib().pleas_lsap_host(A.data_ptr(), int(A.dtype == torch.float64), A.shape[0], int(bool(maximize)),
                                      out.data_ptr()), "pleas_lsap_host")
     return out
@@ -336,22 +411,11 @@ def solve_bottleneck_batched(costs: Sequence[torch.Tensor], maximize: bool = Tru
     it, for :func:`check_bottleneck_status` once the caller reads the results anyway."""
     if not costs:
         return []
-    _need_gpu(*costs)
-    mats = []
-    for c in costs:
-        if c.dim() != 2 or c.shape[0] != c.shape[1] or c.shape[0] < 1:
-            raise PleasHipError("square cost matrices expected, got %s" % (tuple(c.shape),))
-        if c.shape[0] > _lib.LSAP_MAX_N:
-            raise PleasHipError("n = %d exceeds PLEAS_LSAP_MAX_N = %d" % (c.shape[0], _lib.LSAP_MAX_N))
-        mats.append(c.contiguous())
+    mats, outs, cost_ptrs, out_ptrs, ns = _square_costs(costs, 1)
     k = len(mats)
     if t_out is not None and (not t_out.is_cuda or t_out.dtype != torch.float32 or t_out.numel() != k
                               or not t_out.is_contiguous()):
         raise PleasHipError("t_out must be a contiguous fp32 device tensor of %d elements" % k)
-    outs = [torch.empty(m.shape[0], dtype=torch.int64, device=m.device) for m in mats]
-    cost_ptrs = (ctypes.c_void_p * k)(*[m.data_ptr() for m in mats])
-    out_ptrs = (ctypes.c_void_p * k)(*[o.data_ptr() for o in outs])
-    ns = (ctypes.c_int * k)(*[m.shape[0] for m in mats])
     lib = _lib.lib()
     nbytes = lib.pleas_bottleneck_ws_bytes(ns, k)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mats[0].device)        # caching allocator, current stream
@@ -375,50 +439,48 @@ def hip_solve_minimax_assignment(A: torch.Tensor, maximize: bool = True) -> torc
 def host_solve_minimax_assignment(A: torch.Tensor, maximize: bool = True) -> torch.Tensor:
     """``pleas_bottleneck_host``: the same contract on a HOST matrix (fp32 / fp64 CPU tensor), synchronous, same
     ``col_ind`` as the device path.  Device tensors are refused."""
-    if A.is_cuda:
-        raise PleasHipError("host_solve_minimax_assignment takes a CPU tensor; use hip_solve_minimax_assignment for "
-                            "device tensors")
-    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
-        raise PleasHipError("square cost matrix expected, got %s" % (tuple(A.shape),))
-    if A.dtype not in (torch.float32, torch.float64):
-        A = A.double()
-    A = A.contiguous()
-    out = torch.empty(A.shape[0], dtype=torch.int64)
+    A, out = _host_cost(A, "host_solve_minimax_assignment", "hip_solve_minimax_assignment")
     check(_lib.lib().pleas_bottleneck_host(A.data_ptr(), int(A.dtype == torch.float64), A.shape[0], int(bool(maximize)),
                                            out.data_ptr(), None), "pleas_bottleneck_host")
     return out
 
 
 # ---------------------------------------------------------------------------------------- bn + add + relu
+def _bn_act_args(name: str, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor]):
+    """Checks shared by ``bn_act`` and ``bn_act_tracked``: returns ``(x, res, C, batches)``, x and res contiguous.  scale / shift
+    ``[batches][C]``: x holds that many batches back to back along dim 0, each with its own affine map."""
+    _need_gpu(x, scale, shift)
+    if x.dim() < 2:
+        raise PleasHipError("%s needs an fp32 [N, C, ...] tensor" % name)
+    x = x.contiguous()
+    if res is not None:
+        if res.shape != x.shape or res.dtype != torch.float32:
+            raise PleasHipError("%s: residual shape/dtype differs from x" % name)
+        res = res.contiguous()
+    C = x.shape[1]
+    batches = scale.shape[0] if scale.dim() == 2 else 1
+    if scale.numel() != batches * C or shift.shape != scale.shape or not scale.is_contiguous() or not shift.is_contiguous():
+        raise PleasHipError("%s: scale/shift must be contiguous with one entry per channel (and batch)" % name)
+    if x.shape[0] % batches:
+        raise PleasHipError("%s: %d samples do not split into %d batches" % (name, x.shape[0], batches))
+    return x, res, C, batches
+
+
 def bn_act(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor] = None,
            relu: bool = True) -> torch.Tensor:
     """``act(x * scale[c] + shift[c] (+ res))`` over dim 1 of a contiguous fp32 tensor: inference BatchNorm,
     residual add and ReLU of a frozen source model in one pass (``pleas_bn_act``)."""
-    _need_gpu(x, scale, shift)
-    if x.dim() < 2 or x.dtype != torch.float32:
-        raise PleasHipError("bn_act needs an fp32 [N, C, ...] tensor")
-    x = x.contiguous()
-    if res is not None:
-        if res.shape != x.shape or res.dtype != torch.float32:
-            raise PleasHipError("bn_act: residual shape/dtype differs from x")
-        res = res.contiguous()
-    C = x.shape[1]
-    # scale / shift [batches][C]: x holds that many batches back to back along dim 0, each with its own affine map
-    batches = scale.shape[0] if scale.dim() == 2 else 1
-    if scale.numel() != batches * C or shift.shape != scale.shape or not scale.is_contiguous() or not shift.is_contiguous():
-        raise PleasHipError("bn_act: scale/shift must be contiguous with one entry per channel (and batch)")
-    if x.shape[0] % batches:
-        raise PleasHipError("bn_act: %d samples do not split into %d batches" % (x.shape[0], batches))
+    x, res, C, batches = _bn_act_args("bn_act", x, scale, shift, res)
     y = torch.empty_like(x)
     ptr = res.data_ptr() if res is not None else None
     if batches == 1:
-        rc = _lib.lib().pleas_bn_act(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), ptr, y.data_ptr(), x.shape[0], C,
-                                     math.prod(x.shape[2:]), int(relu), _stream())
+        check(_lib.lib().pleas_bn_act(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), ptr, y.data_ptr(), x.shape[0], C,
+                                      math.prod(x.shape[2:]), int(relu), _stream()), "pleas_bn_act")
     else:      # the tracked pass without its optional outputs is this pass
-        rc = _lib.lib().pleas_bn_act_tracked_batches(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), ptr, None, None,
-                                                     y.data_ptr(), x.shape[0] // batches, batches, C,
-                                                     math.prod(x.shape[2:]), int(relu), _stream())
-    _lib.check(rc, "pleas_bn_act")
+        check(_lib.lib().pleas_bn_act_tracked_batches(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), ptr, None, None,
+                                                      y.data_ptr(), x.shape[0] // batches, batches, C,
+                                                      math.prod(x.shape[2:]), int(relu), _stream()),
+              "pleas_bn_act_tracked_batches")
     return y
 
 
@@ -441,7 +503,7 @@ def bn_act_maxpool(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Option
     rc = _lib.lib().pleas_bn_act_maxpool(x.data_ptr(), scale.data_ptr() if scale is not None else None,
                                          shift.data_ptr() if scale is not None else None, y.data_ptr(), N, C, H, W, KH, KW,
                                          stride, padding, int(relu), _stream())
-    _lib.check(rc, "pleas_bn_act_maxpool")
+    check(rc, "pleas_bn_act_maxpool")
     return y
 
 
@@ -451,19 +513,7 @@ def bn_act_tracked(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, re
     ``sum`` is None without a residual and ``act`` is None without ``relu`` (``pleas_bn_act_tracked``).
     ``keep_bn=False``: the BatchNorm value itself is not needed by the caller (its matching cost is derived from the
     convolution node, ``GramBatch.add_derived``) and is not written unless it is the chain's last value."""
-    _need_gpu(x, scale, shift)
-    x = x.contiguous()
-    if res is not None:
-        if res.shape != x.shape or res.dtype != torch.float32:
-            raise PleasHipError("bn_act_tracked: residual shape/dtype differs from x")
-        res = res.contiguous()
-    C = x.shape[1]
-    # scale / shift [batches][C]: x holds that many batches back to back along dim 0, each with its own affine map
-    batches = scale.shape[0] if scale.dim() == 2 else 1
-    if scale.numel() != batches * C or shift.shape != scale.shape or not scale.is_contiguous() or not shift.is_contiguous():
-        raise PleasHipError("bn_act_tracked: scale/shift must hold one entry per channel (and batch)")
-    if x.shape[0] % batches:
-        raise PleasHipError("bn_act_tracked: %d samples do not split into %d batches" % (x.shape[0], batches))
+    x, res, C, batches = _bn_act_args("bn_act_tracked", x, scale, shift, res)
     # the last value of the chain goes to `y`; earlier ones to the optional outputs
     y_bn = torch.empty_like(x) if ((res is not None or relu) and keep_bn) else None
     y_sum = torch.empty_like(x) if (res is not None and relu) else None
@@ -479,6 +529,23 @@ def bn_act_tracked(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, re
     return (y_bn, y_sum, y) if relu else (y_bn, y, None)
 
 
+def _bn_train_args(bn: "torch.nn.BatchNorm2d", x: torch.Tensor, batches: int = 1):
+    """Checks and addresses shared by ``bn_train_fold`` and ``BnTrainFold``: ``(n, C, inner, pointers)`` with ``n`` samples per
+    batch and ``pointers`` = weight, bias, running mean, running variance, batch counter (None where absent or untracked)."""
+    if x.shape[0] % batches:
+        raise PleasHipError("bn_train_fold: %d samples do not split into %d batches" % (x.shape[0], batches))
+    n, C = x.shape[0] // batches, x.shape[1]
+    inner = math.prod(x.shape[2:])
+    if n * inner <= 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    track = bn.track_running_stats and bn.running_mean is not None
+    tensors = (bn.weight, bn.bias) + ((bn.running_mean, bn.running_var, bn.num_batches_tracked) if track else (None, None, None))
+    for t in tensors[:4]:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device):
+            raise PleasHipError("bn_train_fold: BatchNorm parameters / buffers must be contiguous fp32 on x's device")
+    return n, C, inner, tuple(t.data_ptr() if t is not None else None for t in tensors)
+
+
 def bn_train_fold(bn: "torch.nn.BatchNorm2d", x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """Train-mode ``bn`` on ``x`` as a per-channel affine map: returns fp32 device vectors ``(scale, shift)`` with
     ``F.batch_norm(x, ..., training=True) == x * scale[c] + shift[c]`` and updates ``bn``'s running statistics and
@@ -488,23 +555,13 @@ def bn_train_fold(bn: "torch.nn.BatchNorm2d", x: torch.Tensor) -> Tuple[torch.Te
     if x.dim() < 2:
         raise PleasHipError("bn_train_fold needs an [N, C, ...] tensor")
     x = x.contiguous()
-    n, C = x.shape[0], x.shape[1]
-    inner = math.prod(x.shape[2:])
-    if n * inner <= 1:
-        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    n, C, inner, (w, b, rm, rv, nbt) = _bn_train_args(bn, x)
     lib = _lib.lib()
     need = int(lib.pleas_bn_train_ws_bytes(n, C))
     ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
     out = torch.empty(2, C, dtype=torch.float32, device=x.device)
-    track = bn.track_running_stats and bn.running_mean is not None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    for t in (bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device):
-            raise PleasHipError("bn_train_fold: BatchNorm parameters / buffers must be contiguous fp32 on x's device")
-    rc = lib.pleas_bn_train_fold(x.data_ptr(), n, C, inner, ptr(bn.weight), ptr(bn.bias), float(bn.eps),
-                                 -1.0 if bn.momentum is None else float(bn.momentum),
-                                 ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                                 ptr(bn.num_batches_tracked) if (track and bn.num_batches_tracked is not None) else None,
+    rc = lib.pleas_bn_train_fold(x.data_ptr(), n, C, inner, w, b, float(bn.eps),
+                                 -1.0 if bn.momentum is None else float(bn.momentum), rm, rv, nbt,
                                  out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), need, _stream())
     check(rc, "pleas_bn_train_fold")
     return out[0], out[1]
@@ -523,24 +580,12 @@ class BnTrainFold:
 
     def _prepare(self, x: torch.Tensor, batches: int) -> None:
         bn = self.bn
-        if x.shape[0] % batches:
-            raise PleasHipError("bn_train_fold: %d samples do not split into %d batches" % (x.shape[0], batches))
-        n, C = x.shape[0] // batches, x.shape[1]
-        inner = math.prod(x.shape[2:])
-        if n * inner <= 1:
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
-        track = bn.track_running_stats and bn.running_mean is not None
-        for t in (bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None):
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device):
-                raise PleasHipError("bn_train_fold: BatchNorm parameters / buffers must be contiguous fp32 on x's device")
+        n, C, inner, (w, b, rm, rv, nbt) = _bn_train_args(bn, x, batches)
         need = batches * int(_lib.lib().pleas_bn_train_ws_bytes(n, C))
         self._ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
         self._out = torch.empty(2, batches, C, dtype=torch.float32, device=x.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None
         self._tensors = self._addresses()      # compared per call: Module._apply swaps .data under the same objects
-        self._args = (n, batches, C, inner, ptr(bn.weight), ptr(bn.bias), float(bn.eps),
-                      ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                      ptr(bn.num_batches_tracked) if (track and bn.num_batches_tracked is not None) else None,
+        self._args = (n, batches, C, inner, w, b, float(bn.eps), rm, rv, nbt,
                       self._out[0].data_ptr(), self._out[1].data_ptr(), self._ws.data_ptr(), need)
         self._shape = (tuple(x.shape), x.device, batches)
 
@@ -679,17 +724,11 @@ def loss_final(partials: torch.Tensor, n_partials: torch.Tensor, scale: torch.Te
     check(rc, "pleas_loss_final")
 
 
-class MergeBatch:
+class MergeBatch(_GroupedLaunch):
     """Block gather / average of many tensors along one axis in ONE grouped launch (``pleas_merge_batch``): the merged
     inputs of all layers of a PLeaS update.  ``add`` returns the output tensor (filled at ``flush``)."""
 
-    def __init__(self, device: torch.device):
-        self.device = device
-        self._keep: list = []
-        self._geo: list = []
-        self._arr = None
-        self._ws = None
-        self._fresh = 1
+    STRUCT, WS_BYTES, LAUNCH = _lib.MergeItem, "pleas_merge_batch_ws_bytes", "pleas_merge_batch"
 
     def add(self, w1: torch.Tensor, w2: torch.Tensor, row_axis: int, row1: torch.Tensor, row2: torch.Tensor,
             n_merged_rows: int, out: Optional[torch.Tensor] = None, subsample: int = 1) -> torch.Tensor:
@@ -712,53 +751,13 @@ class MergeBatch:
             out = torch.empty(want, dtype=torch.float32, device=w1.device)
         elif list(out.shape) != want or out.dtype != torch.float32 or not out.is_contiguous() or out.device != w1.device:
             raise PleasHipError("MergeBatch.add: out must be a contiguous fp32 tensor of shape %s" % (want,))
-        self._keep.append((w1, w2, out, row1, row2))
-        self._geo.append((math.prod(shape[:row_axis]), math.prod(want[row_axis + 1:]), rows_out, shape[row_axis],
-                          int(n_merged_rows)) + sub)
+        self._queue((w1, w2, out, row1, row2), (math.prod(shape[:row_axis]), math.prod(want[row_axis + 1:]), rows_out,
+                                                shape[row_axis], int(n_merged_rows)) + sub)
         return out
 
-    def flush(self) -> None:
-        n = len(self._keep)
-        if n == 0:
-            return
-        if self._arr is None or len(self._arr) != n:
-            self._arr = (_lib.MergeItem * n)()
-        for i, ((w1, w2, out, row1, row2), geo) in enumerate(zip(self._keep, self._geo)):
-            a = self._arr[i]
-            a.w1, a.w2, a.out, a.row1, a.row2 = w1.data_ptr(), w2.data_ptr(), out.data_ptr(), row1.data_ptr(), row2.data_ptr()
-            a.outer, a.inner, a.rows_out, a.rows_src, a.n_merged, a.sub_stride, a.sub_h, a.sub_w = geo
-        lib = _lib.lib()
-        if self._ws is None:
-            need = int(lib.pleas_merge_batch_ws_bytes(self._arr, n))
-            if need == 0:
-                raise PleasHipError("pleas_merge_batch_ws_bytes rejected the tensor list: %s" % lib.pleas_last_error().decode())
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._fresh = 1
-        rc = lib.pleas_merge_batch(self._arr, n, self._ws.data_ptr(), self._ws.numel(), self._fresh, _stream())
-        self._fresh = 0
-        if rc == -12:
-            self._ws = None
-            self.flush()
-            return
-        check(rc, "pleas_merge_batch")
-        self._keep.clear()
-        self._geo.clear()
-
-
-
-    def table(self):
-        """numpy view of the item table of the latest ``flush`` (shares its memory): pointer fields may be rewritten before
-        ``relaunch`` -- the per-update fast path of ``PleasFitter``, which keeps every other field as it is."""
-        import numpy as np
-
-        return None if self._arr is None else np.frombuffer(self._arr, dtype=np.dtype(type(self._arr[0])))
-
-    def relaunch(self) -> None:
-        """The launch of the latest ``flush`` again, with the table as it is now."""
-        if self._keep or self._arr is None or self._ws is None:
-            raise PleasHipError("MergeBatch.relaunch: nothing flushed yet, or tensors pending")
-        check(_lib.lib().pleas_merge_batch(self._arr, len(self._arr), self._ws.data_ptr(), self._ws.numel(), 0, _stream()),
-              "pleas_merge_batch")
+    def _fill(self, a, tensors, geo) -> None:
+        a.w1, a.w2, a.out, a.row1, a.row2 = (t.data_ptr() for t in tensors)
+        a.outer, a.inner, a.rows_out, a.rows_src, a.n_merged, a.sub_stride, a.sub_h, a.sub_w = geo
 
 
 def fwd_plan_lanes() -> dict:
@@ -769,18 +768,11 @@ def fwd_plan_lanes() -> dict:
     return {"state": state, "forms": {f: {"ms": round(ms[f], 4), "lane": lane[f], "items": items[f]} for f in range(10) if items[f]}}
 
 
-class FwdBatch:
+class FwdBatch(_GroupedLaunch):
     """Forward + target + residual + loss of all merged layers of one update in ONE grouped launch
     (``pleas_fwd_batch``).  ``add`` per layer, ``flush(loss)`` once per update."""
 
-    def __init__(self, device: torch.device):
-        self.device = device
-        self._keep: list = []
-        self._geo: list = []
-        self._arr = None
-        self._ws = None
-        self._fresh = 1
-
+    STRUCT, WS_BYTES, LAUNCH = _lib.FwdLayer, "pleas_fwd_batch_ws_bytes", "pleas_fwd_batch"
     KPOS_MAJOR = 1   # w is [Cout][KH][KW][Cin] (needs Cin % 32 == 0)
 
     def add(self, ip, w, bias, o1, o2, row1, row2, n_merged: int, resid, dscale: float, loss_scale: float,
@@ -790,57 +782,33 @@ class FwdBatch:
                 raise PleasHipError("FwdBatch.add: contiguous tensors expected")
         N, Cin = ip.shape[0], ip.shape[1]
         Hin, Win = (ip.shape[2], ip.shape[3]) if ip.dim() == 4 else (1, 1)
-        self._keep.append((ip, w, bias, o1, o2, row1, row2, resid))
-        self._geo.append((N, w.shape[0], Cin, Hin, Win, kernel[0], kernel[1], stride, pad, o1.shape[1], int(n_merged),
-                          float(dscale), float(loss_scale), int(flags)))
+        self._queue((ip, w, bias, o1, o2, row1, row2, resid),
+                    (N, w.shape[0], Cin, Hin, Win, kernel[0], kernel[1], stride, pad, o1.shape[1], int(n_merged),
+                     float(dscale), float(loss_scale), int(flags)))
+
+    def _fill(self, a, tensors, geo) -> None:
+        a.ip, a.w, a.bias, a.o1, a.o2, a.row1, a.row2, a.resid = (t.data_ptr() if t is not None else None for t in tensors)
+        (a.N, a.Cout, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad, a.Csrc, a.n_merged, a.dscale, a.loss_scale,
+         a.flags) = geo
+
+    def _launch_args(self, loss: torch.Tensor) -> tuple:
+        if loss.numel() != len(self._arr) or not loss.is_contiguous():
+            raise PleasHipError("FwdBatch: loss must hold one float per layer")
+        return (loss.data_ptr(),)
 
     def flush(self, loss: torch.Tensor) -> None:
-        n = len(self._keep)
-        if n == 0:
-            return
-        if loss.numel() != n or not loss.is_contiguous():
-            raise PleasHipError("FwdBatch.flush: loss must hold one float per layer")
-        if self._arr is None or len(self._arr) != n:
-            self._arr = (_lib.FwdLayer * n)()
-        for i, (t, geo) in enumerate(zip(self._keep, self._geo)):
-            a = self._arr[i]
-            ip, w, bias, o1, o2, row1, row2, resid = t
-            a.ip, a.w, a.bias = ip.data_ptr(), w.data_ptr(), (bias.data_ptr() if bias is not None else None)
-            a.o1, a.o2, a.row1, a.row2, a.resid = o1.data_ptr(), o2.data_ptr(), row1.data_ptr(), row2.data_ptr(), resid.data_ptr()
-            (a.N, a.Cout, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad, a.Csrc, a.n_merged, a.dscale,
-             a.loss_scale, a.flags) = geo
-        lib = _lib.lib()
-        if self._ws is None:
-            need = int(lib.pleas_fwd_batch_ws_bytes(self._arr, n))
-            if need == 0:
-                raise PleasHipError("pleas_fwd_batch_ws_bytes rejected the layer list: %s" % lib.pleas_last_error().decode())
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._fresh = 1
-        rc = lib.pleas_fwd_batch(self._arr, n, loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(), self._fresh, _stream())
-        self._fresh = 0
-        if rc == -12:
-            self._ws = None
-            self.flush(loss)
-            return
-        check(rc, "pleas_fwd_batch")
-        self._keep.clear()
-        self._geo.clear()
+        self._flush(loss)
 
 
-
-    def table(self):
-        """numpy view of the item table of the latest ``flush`` (shares its memory): pointer fields may be rewritten before
-        ``relaunch`` -- the per-update fast path of ``PleasFitter``, which keeps every other field as it is."""
-        import numpy as np
-
-        return None if self._arr is None else np.frombuffer(self._arr, dtype=np.dtype(type(self._arr[0])))
-
-    def relaunch(self, loss: torch.Tensor) -> None:
-        """The launch of the latest ``flush`` again, with the table as it is now."""
-        if self._keep or self._arr is None or self._ws is None or loss.numel() != len(self._arr):
-            raise PleasHipError("FwdBatch.relaunch: nothing flushed yet, tensors pending, or loss of another length")
-        check(_lib.lib().pleas_fwd_batch(self._arr, len(self._arr), loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(), 0,
-                                         _stream()), "pleas_fwd_batch")
+def _conv_geometry(name: str, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, kpos_major: bool):
+    """``(N, Cin, H, W, Cout, KH, KW, Ho, Wo)`` of a dense square convolution of contiguous 4-D tensors."""
+    if x.dim() != 4 or w.dim() != 4 or not x.is_contiguous() or not w.is_contiguous():
+        raise PleasHipError("%s: contiguous 4-D tensors expected" % name)
+    N, Cin, H, W = x.shape
+    KH, KW = (w.shape[1], w.shape[2]) if kpos_major else (w.shape[2], w.shape[3])
+    if (w.shape[3] if kpos_major else w.shape[1]) != Cin:
+        raise PleasHipError("%s: %d input channels vs a weight of %s" % (name, Cin, tuple(w.shape)))
+    return N, Cin, H, W, w.shape[0], KH, KW, (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int, kpos_major: bool = False,
@@ -850,14 +818,7 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], strid
     kernels are not (they split K with atomics on small images / batches; tools/r05/probe_conv_classes.py).
     ``kpos_major``: ``w`` is ``[Cout][KH][KW][Cin]`` (needs Cin % 32 == 0; the flat-shift forms of stride-1 layers)."""
     _need_gpu(x, w)
-    if x.dim() != 4 or w.dim() != 4 or not x.is_contiguous() or not w.is_contiguous():
-        raise PleasHipError("conv2d: contiguous 4-D tensors expected")
-    N, Cin, H, W = x.shape
-    Cout = w.shape[0]
-    KH, KW = (w.shape[1], w.shape[2]) if kpos_major else (w.shape[2], w.shape[3])
-    if (w.shape[3] if kpos_major else w.shape[1]) != Cin:
-        raise PleasHipError("conv2d: %d input channels vs a weight of %s" % (Cin, tuple(w.shape)))
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d", x, w, stride, pad, kpos_major)
     if out is None:
         out = torch.empty((N, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
     check(_lib.lib().pleas_conv2d_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
@@ -871,14 +832,7 @@ def conv2d_bn_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
     """``y = conv2d(x, w, bias)`` and ``z = bn_act(y, scale, shift, res, relu)`` from ONE launch (``pleas_conv2d_bn_act_fwd``):
     the activated image is written from the registers that hold y, bit for bit what ``bn_act`` makes of y.  Returns ``(y, z)``."""
     _need_gpu(x, w, scale, shift)
-    if x.dim() != 4 or w.dim() != 4 or not x.is_contiguous() or not w.is_contiguous():
-        raise PleasHipError("conv2d_bn_act: contiguous 4-D tensors expected")
-    N, Cin, H, W = x.shape
-    Cout = w.shape[0]
-    KH, KW = (w.shape[1], w.shape[2]) if kpos_major else (w.shape[2], w.shape[3])
-    if (w.shape[3] if kpos_major else w.shape[1]) != Cin:
-        raise PleasHipError("conv2d_bn_act: %d input channels vs a weight of %s" % (Cin, tuple(w.shape)))
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d_bn_act", x, w, stride, pad, kpos_major)
     if scale.numel() != Cout or shift.numel() != Cout or scale.dtype != torch.float32 or shift.dtype != torch.float32:
         raise PleasHipError("conv2d_bn_act: scale / shift must be fp32 vectors of %d channels" % Cout)
     if res is not None and (tuple(res.shape) != (N, Cout, Ho, Wo) or res.dtype != torch.float32 or not res.is_contiguous()
@@ -894,17 +848,11 @@ def conv2d_bn_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
     return y, z
 
 
-class WgradBatch:
+class WgradBatch(_GroupedLaunch):
     """Weight gradients of all merged layers of one update in ONE grouped launch (``pleas_wgrad_batch``).
     ``add`` per layer (operands must stay unmodified until ``flush``), ``flush`` once per update."""
 
-    def __init__(self, device: torch.device):
-        self.device = device
-        self._keep: list = []
-        self._geo: list = []
-        self._arr = None
-        self._ws = None
-
+    STRUCT, WS_BYTES, LAUNCH = _lib.WgradLayer, "pleas_wgrad_batch_ws_bytes", "pleas_wgrad_batch"
     ACCUMULATE, KPOS_MAJOR = 1, 2
 
     def add(self, resid: torch.Tensor, ip: torch.Tensor, grad: torch.Tensor, kernel=(1, 1), stride: int = 1,
@@ -913,44 +861,11 @@ class WgradBatch:
             raise PleasHipError("WgradBatch.add: contiguous tensors expected")
         N, Cout, Cin = resid.shape[0], resid.shape[1], ip.shape[1]
         Hin, Win = (ip.shape[2], ip.shape[3]) if ip.dim() == 4 else (1, 1)
-        self._keep.append((resid, ip, grad))
-        self._geo.append((N, Cout, Cin, Hin, Win, kernel[0], kernel[1], stride, pad, flags))
+        self._queue((resid, ip, grad), (N, Cout, Cin, Hin, Win, kernel[0], kernel[1], stride, pad, flags))
 
-    def flush(self) -> None:
-        n = len(self._keep)
-        if n == 0:
-            return
-        if self._arr is None or len(self._arr) != n:
-            self._arr = (_lib.WgradLayer * n)()
-        for i, ((resid, ip, grad), geo) in enumerate(zip(self._keep, self._geo)):
-            a = self._arr[i]
-            a.resid, a.ip, a.grad = resid.data_ptr(), ip.data_ptr(), grad.data_ptr()
-            a.N, a.Cout, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad, a.flags = geo
-        lib = _lib.lib()
-        if self._ws is None:
-            need = int(lib.pleas_wgrad_batch_ws_bytes(self._arr, n))
-            if need == 0:
-                raise PleasHipError("pleas_wgrad_batch_ws_bytes rejected the layer list: %s" % lib.pleas_last_error().decode())
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._fresh = 1
-        rc = lib.pleas_wgrad_batch(self._arr, n, self._ws.data_ptr(), self._ws.numel(), self._fresh, _stream())
-        self._fresh = 0
-        if rc == -12:
-            self._ws = None
-            self.flush()
-            return
-        check(rc, "pleas_wgrad_batch")
-        self._keep.clear()
-        self._geo.clear()
-
-
-
-    def table(self):
-        """numpy view of the item table of the latest ``flush`` (shares its memory): pointer fields may be rewritten before
-        ``relaunch`` -- the per-update fast path of ``PleasFitter``, which keeps every other field as it is."""
-        import numpy as np
-
-        return None if self._arr is None else np.frombuffer(self._arr, dtype=np.dtype(type(self._arr[0])))
+    def _fill(self, a, tensors, geo) -> None:
+        a.resid, a.ip, a.grad = (t.data_ptr() for t in tensors)
+        a.N, a.Cout, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad, a.flags = geo
 
     @staticmethod
     def plan_info(geometries) -> List[dict]:
@@ -970,24 +885,13 @@ class WgradBatch:
         return [{"variant": info[6 * i], "S": info[6 * i + 1], "tiles_cout": info[6 * i + 2], "tiles_cin": info[6 * i + 3],
                  "items": info[6 * i + 4], "rows": bool(info[6 * i + 5])} for i in range(n)]
 
-    def relaunch(self) -> None:
-        """The launch of the latest ``flush`` again, with the table as it is now."""
-        if self._keep or self._arr is None or self._ws is None:
-            raise PleasHipError("WgradBatch.relaunch: nothing flushed yet, or tensors pending")
-        check(_lib.lib().pleas_wgrad_batch(self._arr, len(self._arr), self._ws.data_ptr(), self._ws.numel(), 0, _stream()),
-              "pleas_wgrad_batch")
-
-
-class NormalEqBatch:
+class NormalEqBatch(_GroupedLaunch):
     """A_l += U_l^T U_l for all layers of one batch in ONE grouped launch (``pleas_normal_eq_accum``)."""
 
+    STRUCT, WS_BYTES, LAUNCH = _lib.NeqLayer, "pleas_normal_eq_ws_bytes", "pleas_normal_eq_accum"
+
     def __init__(self, device: torch.device):
-        self.device = device
-        self._keep: list = []
-        self._geo: list = []
-        self._arr = None
-        self._ws = None
-        self._fresh = 1
+        super().__init__(device)
         self._seen: dict = {}      # A's address -> (A, geometry): every matrix this object has accumulated into
 
     def add(self, ip: torch.Tensor, A: torch.Tensor, kernel=(1, 1), stride: int = 1, pad: int = 0) -> None:
@@ -998,15 +902,19 @@ class NormalEqBatch:
         K = kernel[0] * kernel[1] * Cin
         if tuple(A.shape) != (K, K):
             raise PleasHipError("NormalEqBatch.add: A must be (%d, %d)" % (K, K))
-        self._keep.append((ip, A))
-        self._geo.append((N, Cin, Hin, Win, kernel[0], kernel[1], stride, pad))
-        self._seen[A.data_ptr()] = (A, self._geo[-1])
+        geo = (N, Cin, Hin, Win, kernel[0], kernel[1], stride, pad)
+        self._queue((ip, A), geo)
+        self._seen[A.data_ptr()] = (A, geo)
+
+    def _fill(self, a, tensors, geo) -> None:
+        ip, A = tensors
+        a.ip, a.A = (ip.data_ptr() if ip is not None else 0), A.data_ptr()
+        a.N, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad = geo
 
     def _layer_array(self, pairs):
         arr = (_lib.NeqLayer * len(pairs))()
         for a, (A, geo) in zip(arr, pairs):
-            a.ip, a.A = 0, A.data_ptr()
-            a.N, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad = geo
+            self._fill(a, (None, A), geo)
         return arr
 
     def seen(self) -> dict:
@@ -1030,33 +938,6 @@ class NormalEqBatch:
         if pairs:
             check(_lib.lib().pleas_normal_eq_plan_info(self._layer_array(pairs), len(pairs), info), "pleas_normal_eq_plan_info")
         return {"flops": info[0], "flops_executed": info[1], "items": int(info[2]), "blocks_to_finalize": int(info[3])}
-
-    def flush(self) -> None:
-        n = len(self._keep)
-        if n == 0:
-            return
-        if self._arr is None or len(self._arr) != n:
-            self._arr = (_lib.NeqLayer * n)()
-        for i, ((ip, A), geo) in enumerate(zip(self._keep, self._geo)):
-            a = self._arr[i]
-            a.ip, a.A = ip.data_ptr(), A.data_ptr()
-            a.N, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad = geo
-        lib = _lib.lib()
-        if self._ws is None:
-            need = int(lib.pleas_normal_eq_ws_bytes(self._arr, n))
-            if need == 0:
-                raise PleasHipError("pleas_normal_eq_ws_bytes rejected the layer list: %s" % lib.pleas_last_error().decode())
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._fresh = 1
-        rc = lib.pleas_normal_eq_accum(self._arr, n, self._ws.data_ptr(), self._ws.numel(), self._fresh, _stream())
-        self._fresh = 0
-        if rc == -12:
-            self._ws = None
-            self.flush()
-            return
-        check(rc, "pleas_normal_eq_accum")
-        self._keep.clear()
-        self._geo.clear()
 
 
 def cholesky_solve_batched(As: Sequence[torch.Tensor], Bts: Sequence[torch.Tensor], ridge: float = 0.0) -> torch.Tensor:

@@ -920,7 +920,7 @@ class PleasFitter:
             with self.ops.pin_stream():
                 self.wgrad.relaunch()
         else:
-            n_wgrad = len(self.wgrad._keep)
+            n_wgrad = self.wgrad.pending()
             self.wgrad.flush()  # ONE grouped MFMA launch: weight gradients of every merged layer
             if complete and n_wgrad > 0:
                 names = tuple(self.plans[i].name for i in self._fwd_rows)
