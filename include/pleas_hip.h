@@ -443,8 +443,8 @@ void pleas_prof_select(unsigned kernel_mask); /* bit k: record kernel id k (defa
 void pleas_prof_reset(void);
 int pleas_prof_collect(int kernel, int64_t* launches, double* total_ms, double* flops, double* bytes);
 
-/* Tuning hook for experiments: split-K target workgroup count and minimum K chunks per split. */
-void pleas_gram_tune(int target_blocks, int min_chunks_per_split);
+/* Tuning hook for experiments (tools/hipbench): K chunks per work item of the grouped contraction (<= 0: unchanged) and its
+ * item order, 0 = longest first, anything else = the XCD-aware order (< 0: unchanged). */
 void pleas_gram_batch_tune(int item_chunks, int xcd_order);
 /* Arithmetic of the contraction kernels (matching contraction, grouped forward, weight gradient, plain convolution).
  *   PLEAS_ARITH_FP32       (default) exact fp32 MFMA, v_mfma_f32_32x32x2_f32: bitwise an fmaf chain;
@@ -458,9 +458,6 @@ void pleas_gram_batch_tune(int item_chunks, int xcd_order);
 #define PLEAS_ARITH_SPLIT_BF16 1
 void pleas_arith(int mode);
 int pleas_arith_get(void);
-/* round-3 name of pleas_arith(on ? PLEAS_ARITH_SPLIT_BF16 : PLEAS_ARITH_FP32) */
-void pleas_gram_split_bf16(int on);
-void pleas_wgrad_tune(int item_chunks);
 
 #ifdef __cplusplus
 }

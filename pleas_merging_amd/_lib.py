@@ -56,12 +56,9 @@ SIGNATURES = {
     "pleas_prof_reset": (None, []),
     "pleas_prof_collect": (c_int, [c_int, POINTER(c_int64), POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                    POINTER(ctypes.c_double)]),
-    "pleas_gram_tune": (None, [c_int, c_int]),
-    "pleas_gram_split_bf16": (None, [c_int]),
     "pleas_arith": (None, [c_int]),
     "pleas_arith_get": (c_int, []),
     "pleas_gram_batch_tune": (None, [c_int, c_int]),
-    "pleas_wgrad_tune": (None, [c_int]),
     "pleas_target_residual": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                       c_int64, c_float, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
     "pleas_target_residual_max_partials": (c_int, []),

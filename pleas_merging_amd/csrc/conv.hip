@@ -22,17 +22,9 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "nt_tile.hpp"
 
 namespace pleas {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef f32x4 f32x4u __attribute__((aligned(4)));   // 16 bytes at a 4-byte-aligned address: still ONE global_load_dwordx4
-
-constexpr int cBK = 32;
-constexpr int cLds = 36;
-constexpr int cThreads = 256;
 
 struct WgradLayerDev {
     const float* resid;  // [N][Cout][HWo]
@@ -76,10 +68,10 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
     constexpr bool YROWS = YMODE == 3;     // every row of the Y tile has its own (channel, tap): virtual channels
     constexpr int VECY = (YMODE == 1 || YMODE == 3) ? 1 : (YMODE == 2 ? 4 : VECX);
     static_assert(YMODE != 2 || VECX == 4, "the 16-byte shifted form needs HW % 4 == 0, hence vector loads of X too");
-    constexpr int LPR_X = cBK / VECX, RPP_X = cThreads / LPR_X, PASS_X = TM / RPP_X;
-    constexpr int LPR_Y = cBK / VECY, RPP_Y = cThreads / LPR_Y, PASS_Y = TN / RPP_Y;
-    float* As = smem;                    // [2][TM][cLds]
-    float* Bs = smem + 2 * TM * cLds;    // [2][TN][cLds]
+    constexpr int LPR_X = kBK / VECX, RPP_X = kThreads / LPR_X, PASS_X = TM / RPP_X;
+    constexpr int LPR_Y = kBK / VECY, RPP_Y = kThreads / LPR_Y, PASS_Y = TN / RPP_Y;
+    float* As = smem;                    // [2][TM][kLds]
+    float* Bs = smem + 2 * TM * kLds;    // [2][TN][kLds]
     __bf16* As16 = reinterpret_cast<__bf16*>(smem);      // SPLIT: [TM][kSplitRow], then [TN][kSplitRow]
     __bf16* Bs16 = As16 + TM * kSplitRow;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -120,22 +112,17 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
         }
     }
     f32x16 acc[MTM][MTN];
-#pragma unroll
-    for (int a = 0; a < MTM; ++a)
-#pragma unroll
-        for (int b = 0; b < MTN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    nt_zero(acc);
 
     bool kinx = false, kiny = false;
     // (sample, pixel, row, column) of this thread's first pixel of the chunk being loaded, for the X and the Y operand:
-    // ONE set of divisions per work item, then steps of cBK pixels (chunks are loaded in order).  The divisions per chunk --
+    // ONE set of divisions per work item, then steps of kBK pixels (chunks are loaded in order).  The divisions per chunk --
     // two to four, ~25 vector instructions each -- were a third of the loop's vector work, and vector instructions are what
     // the fp32 MFMAs wait for.  Images smaller than a chunk keep the divisions.
     struct Cursor { uint32_t P, n, p; int oh, ow; };
     constexpr bool XHW = YMODE == 2, YHW = YSHIFT || YROWS;      // who needs (row, column)
-    const bool step_ok = L.HWo >= (uint32_t)cBK;
-    const int q32 = cBK / L.Wout, r32 = cBK - q32 * L.Wout;
+    const bool step_ok = L.HWo >= (uint32_t)kBK;
+    const int q32 = kBK / L.Wout, r32 = kBK - q32 * L.Wout;
     auto cur_at = [&](Cursor& k, uint32_t P, bool hw) {
         k.P = P;
         k.n = P / L.HWo;
@@ -148,11 +135,11 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
     };
     auto cur_step = [&](Cursor& k, bool hw) {
         if (!step_ok) {
-            cur_at(k, k.P + cBK, hw);
+            cur_at(k, k.P + kBK, hw);
             return;
         }
-        k.P += cBK;
-        k.p += cBK;
+        k.P += kBK;
+        k.p += kBK;
         if (hw) {
             k.oh += q32;
             k.ow += r32;
@@ -165,8 +152,8 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
         }
     };
     Cursor cx, cy;
-    cur_at(cx, (uint32_t)it.c_begin * cBK + xcol, XHW);
-    cur_at(cy, (uint32_t)it.c_begin * cBK + ycol, YHW);
+    cur_at(cx, (uint32_t)it.c_begin * kBK + xcol, XHW);
+    cur_at(cy, (uint32_t)it.c_begin * kBK + ycol, YHW);
     auto load_chunk = [&](int c) {
         {   // X: residual rows, direct
             (void)c;
@@ -254,8 +241,8 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
         cur_step(cy, YHW);
     };
     auto store_chunk = [&](int buf) {
-        float* a = As + buf * TM * cLds;
-        float* b = Bs + buf * TN * cLds;
+        float* a = As + buf * TM * kLds;
+        float* b = Bs + buf * TN * kLds;
 #pragma unroll
         for (int q = 0; q < PASS_X; ++q) {
             const bool ok = kinx && ((okx >> q) & 1u);
@@ -266,9 +253,9 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
             } else if constexpr (VECX == 4) {
                 f32x4 v = {(ok && (win & 1u)) ? rx[q][0] : 0.f, (ok && (win & 2u)) ? rx[q][1] : 0.f,
                            (ok && (win & 4u)) ? rx[q][2] : 0.f, (ok && (win & 8u)) ? rx[q][3] : 0.f};
-                *reinterpret_cast<f32x4*>(a + row * cLds + xcol) = v;
+                *reinterpret_cast<f32x4*>(a + row * kLds + xcol) = v;
             } else {
-                a[row * cLds + xcol] = ok ? rx[q][0] : 0.f;
+                a[row * kLds + xcol] = ok ? rx[q][0] : 0.f;
             }
         }
 #pragma unroll
@@ -282,79 +269,19 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
             } else if constexpr (YMODE == 2) {
                 const bool rowok = (oky >> q) & 1u;
                 f32x4 v = {rowok ? ry[q][0] : 0.f, rowok ? ry[q][1] : 0.f, rowok ? ry[q][2] : 0.f, rowok ? ry[q][3] : 0.f};
-                *reinterpret_cast<f32x4*>(b + row * cLds + ycol) = v;
+                *reinterpret_cast<f32x4*>(b + row * kLds + ycol) = v;
             } else if constexpr (VECY == 4) {
                 f32x4 v = {ok ? ry[q][0] : 0.f, ok ? ry[q][1] : 0.f, ok ? ry[q][2] : 0.f, ok ? ry[q][3] : 0.f};
-                *reinterpret_cast<f32x4*>(b + row * cLds + ycol) = v;
+                *reinterpret_cast<f32x4*>(b + row * kLds + ycol) = v;
             } else {
-                b[row * cLds + ycol] = ok ? ry[q][0] : 0.f;
+                b[row * kLds + ycol] = ok ? ry[q][0] : 0.f;
             }
         }
     };
-    auto compute = [&](int buf) {
-        if constexpr (SPLIT) {
-            // lane (r, h) of k group g reads k = 16 g + 8 h .. + 7 of its row from each plane: the operand map of the MFMA
-            const __bf16* a16 = As16 + (wm * (TM / 2) + (lane & 31)) * kSplitRow + 8 * (lane >> 5);
-            const __bf16* b16 = Bs16 + (wn * (TN / 2) + (lane & 31)) * kSplitRow + 8 * (lane >> 5);
-#pragma unroll
-            for (int g16 = 0; g16 < cBK / 16; ++g16) {
-                bf16x8_t sa[MTM][3], sb[MTN][3];
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                    for (int s_ = 0; s_ < MTM; ++s_) sa[s_][p] = *reinterpret_cast<const bf16x8_t*>(a16 + s_ * 32 * kSplitRow + p * 32 + g16 * 16);
-#pragma unroll
-                    for (int s_ = 0; s_ < MTN; ++s_) sb[s_][p] = *reinterpret_cast<const bf16x8_t*>(b16 + s_ * 32 * kSplitRow + p * 32 + g16 * 16);
-                }
-#pragma unroll
-                for (int sm = 0; sm < MTM; ++sm)
-#pragma unroll
-                    for (int sn = 0; sn < MTN; ++sn) acc[sm][sn] = split3_mfma(sa[sm], sb[sn], acc[sm][sn]);
-            }
-            return;
-        }
-        const float* a = As + buf * TM * cLds + (wm * (TM / 2) + (lane & 31)) * cLds + 4 * (lane >> 5);
-        const float* b = Bs + buf * TN * cLds + (wn * (TN / 2) + (lane & 31)) * cLds + 4 * (lane >> 5);
-#pragma unroll
-        for (int kk = 0; kk < cBK / 8; ++kk) {
-            f32x4 fa[MTM], fb[MTN];
-#pragma unroll
-            for (int s = 0; s < MTM; ++s) fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * cLds + kk * 8);
-#pragma unroll
-            for (int s = 0; s < MTN; ++s) fb[s] = *reinterpret_cast<const f32x4*>(b + s * 32 * cLds + kk * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int sm = 0; sm < MTM; ++sm)
-#pragma unroll
-                    for (int sn = 0; sn < MTN; ++sn)
-                        acc[sm][sn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], fb[sn][e], acc[sm][sn], 0, 0, 0);
-        }
-    };
-
-    if (it.c_begin < it.c_end) {
-        load_chunk(it.c_begin);
-        store_chunk(0);
-    }
-    __syncthreads();
-    if constexpr (SPLIT) {
-        for (int c = it.c_begin; c < it.c_end; ++c) {
-            const bool more = c + 1 < it.c_end;
-            if (more) load_chunk(c + 1);      // stays in registers while this chunk is multiplied
-            compute(0);
-            __syncthreads();                  // every wave is done reading the image
-            if (more) store_chunk(0);
-            __syncthreads();
-        }
-    } else
-    for (int c = it.c_begin; c < it.c_end; ++c) {
-        const int buf = (c - it.c_begin) & 1;
-        const bool more = c + 1 < it.c_end;
-        if (more) load_chunk(c + 1);
-        compute(buf);
-        if (more) store_chunk(buf ^ 1);
-        __syncthreads();
-    }
+    nt_pipeline<SPLIT>(it.c_begin, it.c_end, load_chunk, store_chunk, [&](int buf) {
+        if constexpr (SPLIT) nt_mma_split<TM, TN>(As16, Bs16, acc);
+        else nt_mma_fp32<TM, TN>(As, Bs, buf, acc);
+    });
 
     // epilogue: direct (S == 1) into the gradient ([Cout][Cin][R], or kernel-position-major [Cout][R][Cin]), else into this
     // split's slab ([S][Cout][R][Cin]).  Wherever the Cin axis is contiguous in the destination (slabs, kernel-position-major
@@ -367,7 +294,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
         // SPLIT tiles of 128 rows stage one 64-row half at a time (the waves of row half h): the staging tile then fits the
         // split images' 52 KB and three workgroups share a CU
         constexpr int HALVES = (SPLIT && TM == 128) ? 2 : 1, HM = TM / HALVES;
-        constexpr int EL = TN + 4, VPT = HM * TN / 4 / cThreads;
+        constexpr int EL = TN + 4, VPT = HM * TN / 4 / kThreads;
         float* Ct = smem;
         const size_t row_len = (size_t)R * L.Cin;          // floats per output channel in the row-contiguous layouts
         gfloat* dst = L.S > 1 ? PLEAS_GLOBAL_W(L.slab) + (size_t)it.split * L.Cout * row_len : PLEAS_GLOBAL_W(L.out);
@@ -393,14 +320,14 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
             if (add) {
 #pragma unroll
                 for (int q = 0; q < VPT; ++q) {
-                    const int v = tid + q * cThreads, lco = v / (TN / 4), lci = (v % (TN / 4)) * 4;
+                    const int v = tid + q * kThreads, lco = v / (TN / 4), lci = (v % (TN / 4)) * 4;
                     const bool in = r0 + lco < L.Cout && j0 + lci < L.Cin;
                     old[q] = *(const __attribute__((address_space(1))) f32x4*)(dst + (in ? (size_t)(r0 + lco) * row_len + (size_t)it.r * L.Cin + j0 + lci : 0));
                 }
             }
 #pragma unroll
             for (int q = 0; q < VPT; ++q) {
-                const int v = tid + q * cThreads, lco = v / (TN / 4), lci = (v % (TN / 4)) * 4;
+                const int v = tid + q * kThreads, lco = v / (TN / 4), lci = (v % (TN / 4)) * 4;
                 if (r0 + lco < L.Cout && j0 + lci < L.Cin) {
                     f32x4 val = *reinterpret_cast<const f32x4*>(Ct + lco * EL + lci);
                     if (add) val += old[q];
@@ -454,7 +381,7 @@ __device__ __forceinline__ void wgrad_dispatch(const WgradLayerDev& L, const Wgr
     else wgrad_tile<TM, TN, 1, 1>(L, it, smem);
 }
 
-__global__ __launch_bounds__(cThreads, 2) void wgrad_batch_kernel(const WgradLayerDev* __restrict__ layers,
+__global__ __launch_bounds__(kThreads, 2) void wgrad_batch_kernel(const WgradLayerDev* __restrict__ layers,
                                                                const WgradItemDev* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const WgradItemDev it = items[blockIdx.x];
@@ -468,7 +395,7 @@ __global__ __launch_bounds__(cThreads, 2) void wgrad_batch_kernel(const WgradLay
     }
 }
 
-__global__ __launch_bounds__(cThreads, 3) void wgrad_batch_split_kernel(const WgradLayerDev* __restrict__ layers,
+__global__ __launch_bounds__(kThreads, 3) void wgrad_batch_split_kernel(const WgradLayerDev* __restrict__ layers,
                                                                      const WgradItemDev* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const WgradItemDev it = items[blockIdx.x];
@@ -600,7 +527,7 @@ __global__ __launch_bounds__(64) void loss_final_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ host plan
-static int g_wgrad_item_chunks = 112;
+constexpr int kWgradItemChunks = 112;      // K chunks per work item
 
 struct WgradPlan {
     std::vector<int64_t> key;
@@ -673,8 +600,8 @@ static int build_wgrad_plan(WgradPlan& P, const pleas_wgrad_layer* ly, int n) {
             d.variant |= 16;
             d.total = (int)total;
         }
-        const int nchunks = (int)ceil_div(K, cBK);
-        const int S = (int)ceil_div(nchunks, g_wgrad_item_chunks);
+        const int nchunks = (int)ceil_div(K, kBK);
+        const int S = (int)ceil_div(nchunks, kWgradItemChunks);
         const int cps = (int)ceil_div(nchunks, S);
         d.S = S;
         if (S > 1) {
@@ -696,7 +623,7 @@ static int build_wgrad_plan(WgradPlan& P, const pleas_wgrad_layer* ly, int n) {
             P.lds_split = std::max(P.lds_split, (size_t)64 * (TN + 4) * sizeof(float));
             P.flops_split += 2.0 * l.Cout * (double)Cin * R * (double)K;
         } else {
-            P.lds = std::max(P.lds, (size_t)2 * (TM + TN) * cLds * sizeof(float));
+            P.lds = std::max(P.lds, (size_t)2 * (TM + TN) * kLds * sizeof(float));
         }
         P.flops += 2.0 * l.Cout * (double)Cin * R * (double)K;
         P.bytes += ((double)l.Cout * K + (double)l.Cin * l.N * HWi) * sizeof(float);
@@ -741,7 +668,7 @@ static std::vector<int64_t> wgrad_key(const pleas_wgrad_layer* ly, int n, const 
     std::vector<int64_t> k;
     k.push_back(n);
     k.push_back((int64_t)(uintptr_t)ws);
-    k.push_back(g_wgrad_item_chunks * 2 + arith_mode());      // plans differ between the arithmetics (pleas_arith)
+    k.push_back(arith_mode());      // plans differ between the arithmetics (pleas_arith)
     for (int i = 0; i < n; ++i) {
         const pleas_wgrad_layer& l = ly[i];
         for (int v : {l.N, l.Cout, l.Cin, l.Hin, l.Win, l.KH, l.KW, l.stride, l.pad, l.flags}) k.push_back(v);
@@ -752,10 +679,6 @@ static std::vector<int64_t> wgrad_key(const pleas_wgrad_layer* ly, int n, const 
 }  // namespace pleas
 
 using namespace pleas;
-
-extern "C" void pleas_wgrad_tune(int item_chunks) {
-    if (item_chunks > 0) g_wgrad_item_chunks = item_chunks;
-}
 
 extern "C" size_t pleas_wgrad_batch_ws_bytes(const pleas_wgrad_layer* layers, int n_layers) {
     if (!layers || n_layers <= 0) return 0;
@@ -845,11 +768,11 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
             st_exact = side.streams[0];
         }
         if (n_exact > 0) {
-            hipLaunchKernelGGL(wgrad_batch_kernel, dim3((unsigned)n_exact), dim3(cThreads), P.lds, st_exact, dl, its + P.n_split);
+            hipLaunchKernelGGL(wgrad_batch_kernel, dim3((unsigned)n_exact), dim3(kThreads), P.lds, st_exact, dl, its + P.n_split);
             PLEAS_LAUNCH_CHECK("wgrad_batch_kernel");
         }
         if (P.n_split > 0) {
-            hipLaunchKernelGGL(wgrad_batch_split_kernel, dim3((unsigned)P.n_split), dim3(cThreads), P.lds_split, stream, dl, its);
+            hipLaunchKernelGGL(wgrad_batch_split_kernel, dim3((unsigned)P.n_split), dim3(kThreads), P.lds_split, stream, dl, its);
             PLEAS_LAUNCH_CHECK("wgrad_batch_split_kernel");
         }
         if (fork) {

@@ -21,18 +21,9 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "nt_tile.hpp"
 
 namespace pleas {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef f32x4 f32x4u __attribute__((aligned(4)));   // 16 bytes at a 4-byte-aligned address: still ONE global_load_dwordx4
-
-constexpr int kBK = 32;      // K chunk (floats) staged per step
-constexpr int kLds = 36;     // padded LDS row stride: 16-B aligned rows, conflict-free ds_read_b128
-constexpr int kThreads = 256;
 
 struct GramGeom {
     const float* x;
@@ -60,24 +51,8 @@ struct Stage {
     float v[PASSES][VEC];
 };
 
-// STUDY arithmetic (SPLIT = 1, off unless pleas_gram_split_bf16(1) / PLEAS_GRAM_SPLIT_BF16=1): an fp32 value as the exact
-// sum of three bf16 values, v = h1 + h2 + h3 (8 + 8 + 8 significant bits, each the round-to-nearest bf16 of what the
-// previous ones left; the exponent range of bf16 is fp32's), so that an fp32 product becomes bf16-MFMA products:
-//   x * y = x1 y1 + (x1 y2 + x2 y1) + (x2 y2 + x1 y3 + x3 y1)  + terms <= 2^-26 |x y| (dropped)
-// Six v_mfma_f32_32x32x16_bf16 (32 cycles each, K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles each, K = 2).
-// The split is done ONCE per element, when a K chunk goes from registers to LDS (three bf16 planes per row, the bytes
-// of an fp32 row and a half); splitting at fragment-read time instead -- every element once per wave that uses it -- was
-// bound by the conversions' issue slots (measured: 0.88 of the fp32 peak).  LDS is single-buffered here (two barriers per
-// chunk, the next chunk waits in registers); two workgroups per CU alternate between converting and multiplying.
-// Not for inf / NaN operands (inf - inf in the residual).
-constexpr int kSplitLd = kSplitRow;      // common.hpp: three bf16 planes per LDS row
-__device__ __forceinline__ void split3(const float (&v)[4], u32x2_t (&h)[3]) {      // h[plane] = four bf16, k order kept
-    uint32_t lo[3], hi[3];
-    split3_pair(v[0], v[1], lo);
-    split3_pair(v[2], v[3], hi);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) h[p] = u32x2_t{lo[p], hi[p]};
-}
+// SPLIT = 1: the split-bf16 arithmetic of pleas_arith (common.hpp); its LDS image is single-buffered (nt_tile.hpp), and two
+// workgroups per CU alternate between converting and multiplying.
 
 // One workgroup's share: output tile (tm, tn) over K chunks [c_begin, c_end) -> slab `split`.
 template <int TILE, int VEC, int SPLIT = 0, int PAD = 0>
@@ -90,11 +65,11 @@ __device__ __forceinline__ void gram_tile(const GramGeom& g, float* smem, const 
     constexpr int PASSES = TILE / ROWS_PER_PASS;
     float* As = smem;                         // [2][TILE][kLds]
     float* Bs = smem + 2 * TILE * kLds;       // [2][TILE][kLds]
-    __bf16* As16 = reinterpret_cast<__bf16*>(smem);      // SPLIT: [TILE][kSplitLd], one buffer per operand
-    __bf16* Bs16 = As16 + TILE * kSplitLd;
+    __bf16* As16 = reinterpret_cast<__bf16*>(smem);      // SPLIT: [TILE][kSplitRow], one buffer per operand
+    __bf16* Bs16 = As16 + TILE * kSplitRow;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = tid >> 6;      // of the epilogue's accumulator layout
     const int wm = wave >> 1, wn = wave & 1;
     const int i0 = tm * TILE, j0 = tn * TILE;
 
@@ -108,20 +83,10 @@ __device__ __forceinline__ void gram_tile(const GramGeom& g, float* smem, const 
     const bool want_sums = g.sums != 0;   // block-uniform
     // EVERY tile does the row-norm / row-sum arithmetic, although only the first block column / row stores it: the tiles of
     // one (node, K range) stream the same operand rows through one XCD's L2 and stay in step only if they do the same work
-    // per chunk.  Round 3 let the other tiles skip it (commit 4ffa37f): they ran ahead, and the launch fetched 15.2 GB
-    // instead of 9.9 GB per ResNet-101 batch for no gain in time (profiles/r04_gram_traffic_bisect.txt; build with
-    // -DPLEAS_GRAM_NORMS_ALWAYS=0 to reproduce).
-#ifndef PLEAS_GRAM_NORMS_ALWAYS
-#define PLEAS_GRAM_NORMS_ALWAYS 1
-#endif
-    const bool norm_a = tn == 0 || PLEAS_GRAM_NORMS_ALWAYS, norm_b = tm == 0 || PLEAS_GRAM_NORMS_ALWAYS;
+    // per chunk.  Tiles that skipped it ran ahead, and the launch fetched 15.2 GB instead of 9.9 GB per ResNet-101 batch for
+    // no gain in time (profiles/r04_gram_traffic_bisect.txt).
     f32x16 acc[MT][MT];
-#pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < MT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    nt_zero(acc);
 
     // Row validity is fixed per thread; loads are UNCONDITIONAL from clamped (always valid) addresses
     // and masked when written to LDS, so all loads of a chunk stay in flight behind the MFMAs
@@ -236,14 +201,8 @@ __device__ __forceinline__ void gram_tile(const GramGeom& g, float* smem, const 
             }
             if constexpr (SPLIT) {
                 static_assert(!SPLIT || VEC == 4, "the split image is written four k at a time");
-                u32x2_t ha[3], hb[3];
-                split3(ra.v[q], ha);
-                split3(rb.v[q], hb);
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    *reinterpret_cast<u32x2_t*>(As16 + row * kSplitLd + p * kBK + scol) = ha[p];
-                    *reinterpret_cast<u32x2_t*>(Bs16 + row * kSplitLd + p * kBK + scol) = hb[p];
-                }
+                split3_store4(As16 + row * kSplitRow, scol, ra.v[q][0], ra.v[q][1], ra.v[q][2], ra.v[q][3]);
+                split3_store4(Bs16 + row * kSplitRow, scol, rb.v[q][0], rb.v[q][1], rb.v[q][2], rb.v[q][3]);
             } else if constexpr (VEC == 4) {
                 f32x4 va = {ra.v[q][0], ra.v[q][1], ra.v[q][2], ra.v[q][3]};
                 f32x4 vb = {rb.v[q][0], rb.v[q][1], rb.v[q][2], rb.v[q][3]};
@@ -253,108 +212,24 @@ __device__ __forceinline__ void gram_tile(const GramGeom& g, float* smem, const 
                 a[row * kLds + scol] = ra.v[q][0];
                 b[row * kLds + scol] = rb.v[q][0];
             }
-            // row norms / sums are stored by the first block column (x rows) and the first block row (y rows) only:
-            // the other tiles skip the arithmetic (block-uniform conditions)
-            if (norm_a) {
 #pragma unroll
-                for (int e = 0; e < VEC; ++e) sqa[q] = fmaf(ra.v[q][e], ra.v[q][e], sqa[q]);
-                if (want_sums) {
+            for (int e = 0; e < VEC; ++e) sqa[q] = fmaf(ra.v[q][e], ra.v[q][e], sqa[q]);
+            if (want_sums) {
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) sma[q] += ra.v[q][e];
-                }
+                for (int e = 0; e < VEC; ++e) sma[q] += ra.v[q][e];
             }
-            if (norm_b) {
 #pragma unroll
-                for (int e = 0; e < VEC; ++e) sqb[q] = fmaf(rb.v[q][e], rb.v[q][e], sqb[q]);
-                if (want_sums) {
+            for (int e = 0; e < VEC; ++e) sqb[q] = fmaf(rb.v[q][e], rb.v[q][e], sqb[q]);
+            if (want_sums) {
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) smb[q] += rb.v[q][e];
-                }
+                for (int e = 0; e < VEC; ++e) smb[q] += rb.v[q][e];
             }
         }
     };
-    auto compute = [&](int buf) {
-        const float* a = As + buf * TILE * kLds + (wm * (TILE / 2) + (lane & 31)) * kLds + 4 * (lane >> 5);
-        const float* b = Bs + buf * TILE * kLds + (wn * (TILE / 2) + (lane & 31)) * kLds + 4 * (lane >> 5);
-        if constexpr (SPLIT) {
-            // lane (r, h) of k group g reads k = 16 g + 8 h .. + 7 of its row from each plane: the operand map of the MFMA
-            const __bf16* a16 = As16 + (wm * (TILE / 2) + (lane & 31)) * kSplitLd + 8 * (lane >> 5);
-            const __bf16* b16 = Bs16 + (wn * (TILE / 2) + (lane & 31)) * kSplitLd + 8 * (lane >> 5);
-#pragma unroll
-            for (int g16 = 0; g16 < kBK / 16; ++g16) {
-                bf16x8 sa[MT][3], sb[MT][3];
-#pragma unroll
-                for (int s = 0; s < MT; ++s)
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        sa[s][p] = *reinterpret_cast<const bf16x8*>(a16 + s * 32 * kSplitLd + p * kBK + g16 * 16);
-                        sb[s][p] = *reinterpret_cast<const bf16x8*>(b16 + s * 32 * kSplitLd + p * kBK + g16 * 16);
-                    }
-#pragma unroll
-                for (int sm = 0; sm < MT; ++sm)
-#pragma unroll
-                    for (int sn = 0; sn < MT; ++sn) {
-                        f32x16 c = acc[sm][sn];      // smallest terms first
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[sm][0], sb[sn][2], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[sm][2], sb[sn][0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[sm][1], sb[sn][1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[sm][0], sb[sn][1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[sm][1], sb[sn][0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[sm][0], sb[sn][0], c, 0, 0, 0);
-                        acc[sm][sn] = c;
-                    }
-            }
-            return;
-        }
-#pragma unroll
-        for (int kk = 0; kk < kBK / 8; ++kk) {
-            f32x4 fa[MT], fb[MT];
-#pragma unroll
-            for (int s = 0; s < MT; ++s) {
-                fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * kLds + kk * 8);
-                fb[s] = *reinterpret_cast<const f32x4*>(b + s * 32 * kLds + kk * 8);
-            }
-            // Lanes 0-31 feed k = 8kk+e, lanes 32-63 feed k = 8kk+4+e: any pairing of k is valid
-            // as long as A and B agree, and it lets one 16-B LDS read serve four MFMA steps.
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int sm = 0; sm < MT; ++sm)
-#pragma unroll
-                    for (int sn = 0; sn < MT; ++sn)
-                        acc[sm][sn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], fb[sn][e], acc[sm][sn], 0, 0, 0);
-        }
-    };
-
-    if (c_begin < c_end) {
-        load_chunk(c_begin);
-        store_chunk(0);
-    }
-    __syncthreads();
-#ifndef PLEAS_GRAM_ABLATE
-#define PLEAS_GRAM_ABLATE 0
-#endif
-    if constexpr (SPLIT) {
-        for (int c = c_begin; c < c_end; ++c) {
-            const bool more = c + 1 < c_end;
-            if (more) load_chunk(c + 1);      // stays in registers while this chunk is multiplied
-            compute(0);
-            __syncthreads();                  // every wave is done reading the image
-            if (more) store_chunk(0);
-            __syncthreads();
-        }
-    } else
-    for (int c = c_begin; c < c_end; ++c) {
-        const int buf = (c - c_begin) & 1;
-        const bool more = c + 1 < c_end;
-        // ablation builds (tools/hipbench): 1 = no global loads, 2 = no MFMA, 3 = no LDS restage/barrier
-        if (more && PLEAS_GRAM_ABLATE != 1 && PLEAS_GRAM_ABLATE != 3) load_chunk(c + 1);
-        if (PLEAS_GRAM_ABLATE != 2) compute(PLEAS_GRAM_ABLATE == 3 ? 0 : buf);
-        if (PLEAS_GRAM_ABLATE != 3) {
-            if (more) store_chunk(buf ^ 1);
-            __syncthreads();
-        }
-    }
+    nt_pipeline<SPLIT>(c_begin, c_end, load_chunk, store_chunk, [&](int buf) {
+        if constexpr (SPLIT) nt_mma_split<TILE, TILE>(As16, Bs16, acc);
+        else nt_mma_fp32<TILE, TILE>(As, Bs, buf, acc);
+    });
 
     // ---- partial tile -> workspace slab `split`
     gfloat* gp = PLEAS_GLOBAL_W(g.gpart) + (size_t)split * g.C * g.C;
@@ -402,29 +277,29 @@ __device__ __forceinline__ void gram_tile(const GramGeom& g, float* smem, const 
     }
 }
 
-// Single-node launch: grid = tiles x tiles x S.
-template <int TILE, int VEC>
-__global__ __launch_bounds__(kThreads) void gram_partial_kernel(const GramGeom g) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+// Single-node launch: grid = tiles x tiles x S.  The exact and the split arithmetic are kernels of their own (here and in the
+// grouped launch), so that the exact kernel's register allocation does not depend on the split one.
+template <int TILE, int VEC, int SPLIT>
+__device__ __forceinline__ void gram_partial_body(const GramGeom& g, float* smem) {
     int bid = blockIdx.x;
     const int tn = bid % g.tiles;
     bid /= g.tiles;
     const int tm = bid % g.tiles;
     const int split = bid / g.tiles;
     const int c_begin = split * g.chunks_per_split;
-    gram_tile<TILE, VEC>(g, smem, tm, tn, split, c_begin, min(c_begin + g.chunks_per_split, g.nchunks));
+    gram_tile<TILE, VEC, SPLIT>(g, smem, tm, tn, split, c_begin, min(c_begin + g.chunks_per_split, g.nchunks));
 }
 
 template <int TILE, int VEC>
-__global__ __launch_bounds__(kThreads) void gram_partial_split_kernel(const GramGeom g) {      // study arithmetic
+__global__ __launch_bounds__(kThreads) void gram_partial_kernel(const GramGeom g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    int bid = blockIdx.x;
-    const int tn = bid % g.tiles;
-    bid /= g.tiles;
-    const int tm = bid % g.tiles;
-    const int split = bid / g.tiles;
-    const int c_begin = split * g.chunks_per_split;
-    gram_tile<TILE, VEC, 1>(g, smem, tm, tn, split, c_begin, min(c_begin + g.chunks_per_split, g.nchunks));
+    gram_partial_body<TILE, VEC, 0>(g, smem);
+}
+
+template <int TILE, int VEC>
+__global__ __launch_bounds__(kThreads) void gram_partial_split_kernel(const GramGeom g) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    gram_partial_body<TILE, VEC, 1>(g, smem);
 }
 
 // ---- grouped launch: every tracked node of a batch in ONE grid --------------------------------
@@ -452,12 +327,7 @@ struct GramItemDev {      // one workgroup of the grouped launch
     int node, tm, tn, split, c_begin, c_end, pad0, pad1;
 };
 
-__global__ __launch_bounds__(kThreads, 2) void gram_batch_kernel(const GramNodeDev* __restrict__ nodes,
-                                                              const GramItemDev* __restrict__ items) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const GramItemDev it = items[blockIdx.x];
-    if (it.node < 0) return;   // padding of the XCD-aware item order
-    const GramNodeDev nd = nodes[it.node];
+__device__ __forceinline__ GramGeom gram_geom(const GramNodeDev& nd) {
     GramGeom g;
     g.x = nd.x;
     g.y = nd.y;
@@ -471,51 +341,38 @@ __global__ __launch_bounds__(kThreads, 2) void gram_batch_kernel(const GramNodeD
     g.HWp = nd.HWp;
     g.Kk = nd.Kk;
     g.bytes = 4u * nd.C * nd.Ktot;
-    g.nchunks = 0;
-    g.chunks_per_split = 0;
-    g.tiles = 0;
+    g.nchunks = g.chunks_per_split = g.tiles = 0;      // the item carries its tile and K range
+    return g;
+}
+
+// SPLIT: the 16-byte-loadable variants (every MFMA-bound node of a ResNet) run the split arithmetic, the others stay exact
+template <int SPLIT>
+__device__ __forceinline__ void gram_batch_body(const GramNodeDev* __restrict__ nodes, const GramItemDev* __restrict__ items,
+                                                float* smem) {
+    const GramItemDev it = items[blockIdx.x];
+    if (it.node < 0) return;   // padding of the XCD-aware item order
+    const GramNodeDev nd = nodes[it.node];
+    const GramGeom g = gram_geom(nd);
     switch (nd.variant) {  // block-uniform
-        case 0: gram_tile<128, 4>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
+        case 0: gram_tile<128, 4, SPLIT>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
         case 1: gram_tile<128, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
-        case 2: gram_tile<64, 4>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
+        case 2: gram_tile<64, 4, SPLIT>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
         case 3: gram_tile<64, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
         case 4: gram_tile<128, 4, 0, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
         default: gram_tile<64, 4, 0, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
     }
 }
 
-// The same grid with the study arithmetic on the 128-wide 16-byte variant (every MFMA-bound node of a ResNet); a kernel of
-// its own so that the exact kernel's register allocation does not depend on it.
+__global__ __launch_bounds__(kThreads, 2) void gram_batch_kernel(const GramNodeDev* __restrict__ nodes,
+                                                              const GramItemDev* __restrict__ items) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    gram_batch_body<0>(nodes, items, smem);
+}
+
 __global__ __launch_bounds__(kThreads, 2) void gram_batch_split_kernel(const GramNodeDev* __restrict__ nodes,
                                                                     const GramItemDev* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const GramItemDev it = items[blockIdx.x];
-    if (it.node < 0) return;
-    const GramNodeDev nd = nodes[it.node];
-    GramGeom g;
-    g.x = nd.x;
-    g.y = nd.y;
-    g.gpart = nd.gpart;
-    g.npart = nd.npart;
-    g.spart = nd.spart;
-    g.sums = nd.sums;
-    g.C = nd.C;
-    g.HW = nd.HW;
-    g.Ktot = nd.Ktot;
-    g.HWp = nd.HWp;
-    g.Kk = nd.Kk;
-    g.bytes = 4u * nd.C * nd.Ktot;
-    g.nchunks = 0;
-    g.chunks_per_split = 0;
-    g.tiles = 0;
-    switch (nd.variant) {
-        case 0: gram_tile<128, 4, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
-        case 1: gram_tile<128, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
-        case 2: gram_tile<64, 4, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
-        case 3: gram_tile<64, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
-        case 4: gram_tile<128, 4, 0, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;      // exact: no split variant
-        default: gram_tile<64, 4, 0, 1>(g, smem, it.tm, it.tn, it.split, it.c_begin, it.c_end); break;
-    }
+    gram_batch_body<1>(nodes, items, smem);
 }
 
 // Writes the per-batch operand pointers into the device node table (kernel arguments carry them,
@@ -617,8 +474,8 @@ struct GramPlan {
     size_t ws_bytes;
 };
 
-static int g_target_blocks = 512;
-static int g_min_chunks = 2;
+constexpr int kTargetBlocks = 512;      // split-K: workgroups aimed at, and the least chunks a split is worth
+constexpr int kMinChunks = 2;
 
 static GramPlan make_plan(int B, int C, int64_t HW, bool aligned) {
     GramPlan p;
@@ -627,9 +484,9 @@ static GramPlan make_plan(int B, int C, int64_t HW, bool aligned) {
     p.tiles = (int)ceil_div(C, p.tile);
     const int64_t K = (int64_t)B * HW;
     p.nchunks = (int)ceil_div(K, kBK);
-    int S = g_target_blocks / (p.tiles * p.tiles);
+    int S = kTargetBlocks / (p.tiles * p.tiles);
     if (S < 1) S = 1;
-    int cap = p.nchunks / g_min_chunks;
+    int cap = p.nchunks / kMinChunks;
     if (cap < 1) cap = 1;
     if (S > cap) S = cap;
     p.cps = (int)ceil_div(p.nchunks, S);
@@ -642,14 +499,8 @@ static GramPlan make_plan(int B, int C, int64_t HW, bool aligned) {
 
 using namespace pleas;
 
-extern "C" void pleas_gram_tune(int target_blocks, int min_chunks_per_split) {
-    if (target_blocks > 0) g_target_blocks = target_blocks;
-    if (min_chunks_per_split > 0) g_min_chunks = min_chunks_per_split;
-}
-
 // the matching contraction under pleas_arith(PLEAS_ARITH_SPLIT_BF16): gram_tile<TILE, 4, SPLIT = 1> on 16-byte-loadable nodes
 static bool split_bf16() { return arith_mode() == 1; }
-extern "C" void pleas_gram_split_bf16(int on) { pleas_arith(on ? PLEAS_ARITH_SPLIT_BF16 : PLEAS_ARITH_FP32); }   // round-3 name
 
 extern "C" size_t pleas_gram_ws_bytes(int B, int C, int64_t HW) {
     if (B <= 0 || C <= 0 || HW <= 0) return 0;
@@ -689,7 +540,7 @@ extern "C" int pleas_gram_accum(const float* x, const float* y, int B, int C, in
     {
     ProfScope prof(kProfGramPartial, 2.0 * C * (double)C * kk, 2.0 * C * kk * sizeof(float), stream);
     if (p.vec == 4 && split_bf16()) {
-        const size_t lds16 = (size_t)2 * p.tile * kSplitLd * sizeof(__bf16);      // 52 KB at tile 128
+        const size_t lds16 = (size_t)2 * p.tile * kSplitRow * sizeof(__bf16);      // 52 KB at tile 128
         if (p.tile == 128)
             hipLaunchKernelGGL((gram_partial_split_kernel<128, 4>), grid, dim3(kThreads), lds16, stream, g);
         else
@@ -719,7 +570,7 @@ extern "C" int pleas_gram_accum(const float* x, const float* y, int B, int C, in
 namespace pleas {
 
 static int g_item_chunks = 112;
-static int g_xcd_order = 2;  // 0: longest first; 1: compact tile block per XCD inside a (node, split); 2: whole (node, split) per XCD
+static int g_xcd_order = 1;  // 0: longest first; else a whole (node, split) per XCD (xcd_order_items)
 
 struct BatchPlan {
     std::vector<int64_t> key;
@@ -749,8 +600,6 @@ static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, floa
     P.lds = 0;
     std::vector<size_t> slab_off(n), spart_off(n);
     size_t slabs = 0;
-    struct Work { double w; GramItemDev it; };
-    std::vector<Work> work;
     std::vector<XcdWork<GramItemDev>> xwork;
     std::vector<char> is_source(n, 0);
     for (int i = 0; i < n; ++i) {
@@ -771,9 +620,8 @@ static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, floa
         const int vec = (HW % 4 == 0) ? 4 : 1;  // operand alignment is checked per call
         const int tiles = (int)ceil_div(C, tile);
         // images with HW % 4 != 0 and at least four pixels: the padded K axis with under-aligned 16-byte loads instead of one
-        // pixel per load (PLEAS_GRAM_PADK=0 keeps the scalar form for A/B)
-        static const bool padk = !(std::getenv("PLEAS_GRAM_PADK") && std::atoi(std::getenv("PLEAS_GRAM_PADK")) == 0);
-        const bool pad = padk && vec == 1 && HW >= 4;
+        // pixel per load
+        const bool pad = vec == 1 && HW >= 4;
         const int64_t HWp = pad ? (HW + 3) / 4 * 4 : HW;
         const int nchunks = (int)ceil_div((int64_t)B * HWp, kBK);
         const int S = (int)ceil_div(nchunks, g_item_chunks);
@@ -807,47 +655,12 @@ static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, floa
         for (int s = 0; s < S; ++s)
             for (int tm = 0; tm < tiles; ++tm)
                 for (int tn = 0; tn < tiles; ++tn) {
-                    Work w;
-                    w.it = GramItemDev{i, tm, tn, s, s * cps, std::min((s + 1) * cps, nchunks), 0, 0};
-                    w.w = (double)(w.it.c_end - w.it.c_begin) * tile * tile;
-                    work.push_back(w);
+                    const GramItemDev it{i, tm, tn, s, s * cps, std::min((s + 1) * cps, nchunks), 0, 0};
                     // every tile of one (node, K range) streams the same operand rows, chunk by chunk and roughly in step
-                    xwork.push_back(XcdWork<GramItemDev>{w.w, (int64_t)i * 65536 + s, w.it});
+                    xwork.push_back(XcdWork<GramItemDev>{(double)(it.c_end - it.c_begin) * tile * tile, (int64_t)i * 65536 + s, it});
                 }
     }
-    if (g_xcd_order == 2) {
-        P.items = xcd_order_items(xwork, GramItemDev{-1, 0, 0, 0, 0, 0, 0, 0});
-    } else {
-        std::stable_sort(work.begin(), work.end(), [](const Work& a, const Work& b) { return a.w > b.w; });
-        P.items.reserve(work.size());
-        for (auto& w : work) P.items.push_back(w.it);
-    }
-    // XCD-aware tile order: workgroups b and b+8 share an XCD (private L2).  Inside every run of
-    // items that belongs to one (node, split), give each XCD a compact sr x sc block of output
-    // tiles, so the operand rows a tile row / column needs are fetched by one L2 instead of eight.
-    if (g_xcd_order == 1) {
-        size_t pos = 0;
-        while (pos < P.items.size()) {
-            size_t end = pos;
-            while (end < P.items.size() && P.items[end].node == P.items[pos].node && P.items[end].split == P.items[pos].split)
-                ++end;
-            const int var_ = P.nodes[P.items[pos].node].variant;
-            const int t = (int)ceil_div(P.nodes[P.items[pos].node].C, (var_ < 2 || var_ == 4) ? 128 : 64);
-            if ((int)(end - pos) == t * t && t >= 4 && (t & (t - 1)) == 0) {
-                int sr = 1, sc = 1;  // sr * sc = t*t/8, as square as possible, sc >= sr
-                for (int area = t * t / 8; sr * sc < area;) (sc <= sr ? sc : sr) *= 2;
-                if (sr > sc) std::swap(sr, sc);
-                const int blocks_c = t / sc;
-                int seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (size_t g = pos; g < end; ++g) {
-                    const int xcd = (int)(g % 8), k = seen[xcd]++;
-                    P.items[g].tm = (xcd / blocks_c) * sr + k / sc;
-                    P.items[g].tn = (xcd % blocks_c) * sc + k % sc;
-                }
-            }
-            pos = end;
-        }
-    }
+    P.items = xcd_order_items(xwork, GramItemDev{-1, 0, 0, 0, 0, 0, 0, 0}, /*by_default=*/g_xcd_order != 0);
     // groups: node lists in first-appearance order, reduce blocks of 256 elements
     int blk = 0;
     for (int g = 0; g < n_groups; ++g) {

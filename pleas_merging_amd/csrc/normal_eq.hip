@@ -30,17 +30,9 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "nt_tile.hpp"
 
 namespace pleas {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef f32x4 f32x4u __attribute__((aligned(4)));   // 16 bytes at a 4-byte-aligned address: still ONE global_load_dwordx4
-
-constexpr int nBK = 32;
-constexpr int nLds = 36;
-constexpr int nThreads = 256;
 
 struct NeqLayerDev {
     const float* ip;  // [N][Cin][Hin][Win]
@@ -62,7 +54,7 @@ struct NeqItemDev {
 // thread's read-modify-writes of A are 16-byte accesses, requested together (the accumulator registers are free by then).
 template <int T>
 __device__ __forceinline__ void neq_store_tile(const NeqLayerDev& L, const NeqItemDev& it, f32x16 (&acc)[T / 64][T / 64], float* smem) {
-    constexpr int MT = T / 64, EL = T + 4, VPT = T * T / 4 / nThreads;   // 16-byte vectors per thread: 16 (T = 128) / 4
+    constexpr int MT = T / 64, EL = T + 4, VPT = T * T / 4 / kThreads;   // 16-byte vectors per thread: 16 (T = 128) / 4
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int i0 = it.tm * T, j0 = it.tn * T;
@@ -83,7 +75,7 @@ __device__ __forceinline__ void neq_store_tile(const NeqLayerDev& L, const NeqIt
         gfloat* slab = PLEAS_GLOBAL_W(L.slab) + ((size_t)it.slot * L.S + it.split) * (T * T);
 #pragma unroll
         for (int q = 0; q < VPT; ++q) {
-            const int v = tid + q * nThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
+            const int v = tid + q * kThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
             *(__attribute__((address_space(1))) f32x4*)(slab + li * T + lj) = *reinterpret_cast<const f32x4*>(Ct + li * EL + lj);
         }
         return;
@@ -93,13 +85,13 @@ __device__ __forceinline__ void neq_store_tile(const NeqLayerDev& L, const NeqIt
         f32x4 old[VPT];
 #pragma unroll
         for (int q = 0; q < VPT; ++q) {
-            const int v = tid + q * nThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
+            const int v = tid + q * kThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
             const bool in = i0 + li < L.Cin && j0 + lj < L.Cin;
             old[q] = *(const __attribute__((address_space(1))) f32x4*)(Ab + (in ? (size_t)li * L.K + lj : 0));
         }
 #pragma unroll
         for (int q = 0; q < VPT; ++q) {
-            const int v = tid + q * nThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
+            const int v = tid + q * kThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
             if (i0 + li < L.Cin && j0 + lj < L.Cin) {
                 const f32x4 add = *reinterpret_cast<const f32x4*>(Ct + li * EL + lj);
                 *(__attribute__((address_space(1))) f32x4*)(Ab + (size_t)li * L.K + lj) = old[q] + add;
@@ -108,7 +100,7 @@ __device__ __forceinline__ void neq_store_tile(const NeqLayerDev& L, const NeqIt
     } else {
 #pragma unroll
         for (int q = 0; q < VPT; ++q) {
-            const int v = tid + q * nThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
+            const int v = tid + q * kThreads, li = v / (T / 4), lj = (v % (T / 4)) * 4;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (i0 + li < L.Cin && j0 + lj + e < L.Cin) Ab[(size_t)li * L.K + lj + e] += Ct[li * EL + lj + e];
@@ -119,11 +111,10 @@ __device__ __forceinline__ void neq_store_tile(const NeqLayerDev& L, const NeqIt
 template <int T, int VEC, bool SHIFT>
 __device__ __forceinline__ void neq_tile(const NeqLayerDev& L, const NeqItemDev& it, float* smem) {
     constexpr int MT = T / 64;
-    constexpr int LPR = nBK / VEC, RPP = nThreads / LPR, PASS = T / RPP;
+    constexpr int LPR = kBK / VEC, RPP = kThreads / LPR, PASS = T / RPP;
     float* As = smem;
-    float* Bs = smem + 2 * T * nLds;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    float* Bs = smem + 2 * T * kLds;
+    const int tid = threadIdx.x;
     const int i0 = it.tm * T, j0 = it.tn * T;
     const uint32_t HWi = (uint32_t)L.Hin * L.Win;
     const int khx = it.rx / L.KW, kwx = it.rx - khx * L.KW, khy = it.ry / L.KW, kwy = it.ry - khy * L.KW;
@@ -141,15 +132,10 @@ __device__ __forceinline__ void neq_tile(const NeqLayerDev& L, const NeqItemDev&
         offb[q] = (uint32_t)min(gj, L.Cin - 1) * HWi;
     }
     f32x16 acc[MT][MT];
-#pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < MT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    nt_zero(acc);
     bool ina = false, inb = false;
     auto load_chunk = [&](int c) {
-        const uint32_t P = (uint32_t)c * nBK + scol;
+        const uint32_t P = (uint32_t)c * kBK + scol;
         const bool in = P < L.Ktot;
         const uint32_t n = in ? P / L.HWo : 0u;
         const uint32_t p = in ? P - n * L.HWo : 0u;
@@ -183,8 +169,8 @@ __device__ __forceinline__ void neq_tile(const NeqLayerDev& L, const NeqItemDev&
         }
     };
     auto store_chunk = [&](int buf) {
-        float* a = As + buf * T * nLds;
-        float* b = Bs + buf * T * nLds;
+        float* a = As + buf * T * kLds;
+        float* b = Bs + buf * T * kLds;
 #pragma unroll
         for (int q = 0; q < PASS; ++q) {
             const bool fa = ina && ((oka >> q) & 1u), fb = inb && ((okb >> q) & 1u);
@@ -192,47 +178,15 @@ __device__ __forceinline__ void neq_tile(const NeqLayerDev& L, const NeqItemDev&
             if constexpr (VEC == 4) {
                 f32x4 va = {fa ? ra[q][0] : 0.f, fa ? ra[q][1] : 0.f, fa ? ra[q][2] : 0.f, fa ? ra[q][3] : 0.f};
                 f32x4 vb = {fb ? rb[q][0] : 0.f, fb ? rb[q][1] : 0.f, fb ? rb[q][2] : 0.f, fb ? rb[q][3] : 0.f};
-                *reinterpret_cast<f32x4*>(a + row * nLds + scol) = va;
-                *reinterpret_cast<f32x4*>(b + row * nLds + scol) = vb;
+                *reinterpret_cast<f32x4*>(a + row * kLds + scol) = va;
+                *reinterpret_cast<f32x4*>(b + row * kLds + scol) = vb;
             } else {
-                a[row * nLds + scol] = fa ? ra[q][0] : 0.f;
-                b[row * nLds + scol] = fb ? rb[q][0] : 0.f;
+                a[row * kLds + scol] = fa ? ra[q][0] : 0.f;
+                b[row * kLds + scol] = fb ? rb[q][0] : 0.f;
             }
         }
     };
-    auto compute = [&](int buf) {
-        const float* a = As + buf * T * nLds + (wm * (T / 2) + (lane & 31)) * nLds + 4 * (lane >> 5);
-        const float* b = Bs + buf * T * nLds + (wn * (T / 2) + (lane & 31)) * nLds + 4 * (lane >> 5);
-#pragma unroll
-        for (int kk = 0; kk < nBK / 8; ++kk) {
-            f32x4 fa[MT], fb[MT];
-#pragma unroll
-            for (int s = 0; s < MT; ++s) {
-                fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * nLds + kk * 8);
-                fb[s] = *reinterpret_cast<const f32x4*>(b + s * 32 * nLds + kk * 8);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int sm = 0; sm < MT; ++sm)
-#pragma unroll
-                    for (int sn = 0; sn < MT; ++sn)
-                        acc[sm][sn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], fb[sn][e], acc[sm][sn], 0, 0, 0);
-        }
-    };
-    if (it.c_begin < it.c_end) {
-        load_chunk(it.c_begin);
-        store_chunk(0);
-    }
-    __syncthreads();
-    for (int c = it.c_begin; c < it.c_end; ++c) {
-        const int buf = (c - it.c_begin) & 1;
-        const bool more = c + 1 < it.c_end;
-        if (more) load_chunk(c + 1);
-        compute(buf);
-        if (more) store_chunk(buf ^ 1);
-        __syncthreads();
-    }
+    nt_pipeline<0>(it.c_begin, it.c_end, load_chunk, store_chunk, [&](int buf) { nt_mma_fp32<T, T>(As, Bs, buf, acc); });
     neq_store_tile<T>(L, it, acc, smem);
 }
 
@@ -240,11 +194,10 @@ __device__ __forceinline__ void neq_tile(const NeqLayerDev& L, const NeqItemDev&
 template <int T, int VEC>
 __device__ __forceinline__ void neq_lag_tile(const NeqLayerDev& L, const NeqItemDev& it, float* smem) {
     constexpr int MT = T / 64;
-    constexpr int LPR = nBK / VEC, RPP = nThreads / LPR, PASS = T / RPP;
+    constexpr int LPR = kBK / VEC, RPP = kThreads / LPR, PASS = T / RPP;
     float* As = smem;
-    float* Bs = smem + 2 * T * nLds;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    float* Bs = smem + 2 * T * kLds;
+    const int tid = threadIdx.x;
     const int i0 = it.tm * T, j0 = it.tn * T;
     const int HW = L.Hin * L.Win;
     const int khx = it.rx / L.KW, kwx = it.rx - khx * L.KW, khy = it.ry / L.KW, kwy = it.ry - khy * L.KW;
@@ -265,16 +218,11 @@ __device__ __forceinline__ void neq_lag_tile(const NeqLayerDev& L, const NeqItem
         offb[q] = min(gj, L.Cin - 1) * HW;
     }
     f32x16 acc[MT][MT];
-#pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < MT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    nt_zero(acc);
     f32x4 ra[PASS], rb0[PASS];                 // VEC == 1: element 0 only
     unsigned win = 0;                          // bit e: pixel e of this thread's run is inside Q
     auto load_chunk = [&](int c) {
-        const uint32_t P = (uint32_t)c * nBK + scol;
+        const uint32_t P = (uint32_t)c * kBK + scol;
         const bool in = P < L.Ktot;
         const int n = in ? (int)(P / (uint32_t)HW) : 0;
         const int p = in ? (int)(P - (uint32_t)n * HW) : 0;
@@ -309,8 +257,8 @@ __device__ __forceinline__ void neq_lag_tile(const NeqLayerDev& L, const NeqItem
         }
     };
     auto store_chunk = [&](int buf) {
-        float* a = As + buf * T * nLds;
-        float* b = Bs + buf * T * nLds;
+        float* a = As + buf * T * kLds;
+        float* b = Bs + buf * T * kLds;
 #pragma unroll
         for (int q = 0; q < PASS; ++q) {
             const bool fa = (oka >> q) & 1u, fb = (okb >> q) & 1u;
@@ -320,51 +268,19 @@ __device__ __forceinline__ void neq_lag_tile(const NeqLayerDev& L, const NeqItem
                             (fa && (win & 4u)) ? ra[q][2] : 0.f, (fa && (win & 8u)) ? ra[q][3] : 0.f};
                 f32x4 vb = rb0[q];
                 if (!fb) vb = f32x4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<f32x4*>(a + row * nLds + scol) = va;
-                *reinterpret_cast<f32x4*>(b + row * nLds + scol) = vb;
+                *reinterpret_cast<f32x4*>(a + row * kLds + scol) = va;
+                *reinterpret_cast<f32x4*>(b + row * kLds + scol) = vb;
             } else {
-                a[row * nLds + scol] = (fa && (win & 1u)) ? ra[q][0] : 0.f;
-                b[row * nLds + scol] = fb ? rb0[q][0] : 0.f;
+                a[row * kLds + scol] = (fa && (win & 1u)) ? ra[q][0] : 0.f;
+                b[row * kLds + scol] = fb ? rb0[q][0] : 0.f;
             }
         }
     };
-    auto compute = [&](int buf) {
-        const float* a = As + buf * T * nLds + (wm * (T / 2) + (lane & 31)) * nLds + 4 * (lane >> 5);
-        const float* b = Bs + buf * T * nLds + (wn * (T / 2) + (lane & 31)) * nLds + 4 * (lane >> 5);
-#pragma unroll
-        for (int kk = 0; kk < nBK / 8; ++kk) {
-            f32x4 fa[MT], fb[MT];
-#pragma unroll
-            for (int s = 0; s < MT; ++s) {
-                fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * nLds + kk * 8);
-                fb[s] = *reinterpret_cast<const f32x4*>(b + s * 32 * nLds + kk * 8);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int sm = 0; sm < MT; ++sm)
-#pragma unroll
-                    for (int sn = 0; sn < MT; ++sn)
-                        acc[sm][sn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], fb[sn][e], acc[sm][sn], 0, 0, 0);
-        }
-    };
-    if (it.c_begin < it.c_end) {
-        load_chunk(it.c_begin);
-        store_chunk(0);
-    }
-    __syncthreads();
-    for (int c = it.c_begin; c < it.c_end; ++c) {
-        const int buf = (c - it.c_begin) & 1;
-        const bool more = c + 1 < it.c_end;
-        if (more) load_chunk(c + 1);
-        compute(buf);
-        if (more) store_chunk(buf ^ 1);
-        __syncthreads();
-    }
+    nt_pipeline<0>(it.c_begin, it.c_end, load_chunk, store_chunk, [&](int buf) { nt_mma_fp32<T, T>(As, Bs, buf, acc); });
     neq_store_tile<T>(L, it, acc, smem);
 }
 
-__global__ __launch_bounds__(nThreads) void neq_batch_kernel(const NeqLayerDev* __restrict__ layers,
+__global__ __launch_bounds__(kThreads) void neq_batch_kernel(const NeqLayerDev* __restrict__ layers,
                                                              const NeqItemDev* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const NeqItemDev it = items[blockIdx.x];
@@ -543,11 +459,11 @@ static int build_neq_plan(NeqPlan& P, const pleas_neq_layer* ly, int n) {
         const bool vec = (direct || lag) && HWo % 4 == 0;
         d.variant = (T == 64 ? 1 : 0) | (vec ? 0 : 2) | (direct ? 0 : lag ? 8 : 4);
         d.total = lag ? (int)((int64_t)l.N * l.Cin * l.Hin * l.Win) : 0;
-        const int nchunks = (int)ceil_div(K, nBK);
+        const int nchunks = (int)ceil_div(K, kBK);
         const int S = (int)ceil_div(nchunks, g_neq_item_chunks);
         const int cps = (int)ceil_div(nchunks, S);
         d.S = S;
-        P.lds = std::max(P.lds, (size_t)4 * T * nLds * sizeof(float));
+        P.lds = std::max(P.lds, (size_t)4 * T * kLds * sizeof(float));
         const int tiles = (int)ceil_div(l.Cin, T);
         int slot = 0;
         slab_off[i] = slabs;
@@ -580,7 +496,7 @@ static int build_neq_plan(NeqPlan& P, const pleas_neq_layer* ly, int n) {
         if (S > 1) slabs += (size_t)slot * S * T * T;
         P.flops += (double)d.K * d.K * (double)K;  // the path's work -- lower triangle: half of 2 K^2 P
         // what the grid executes: whole tiles (ragged ones and the diagonal's upper halves included), lag copies left out
-        P.flops_exec += 2.0 * (double)tiles_done * T * T * (double)nchunks * nBK;
+        P.flops_exec += 2.0 * (double)tiles_done * T * T * (double)nchunks * kBK;
         P.bytes += (double)l.Cin * l.N * l.Hin * l.Win * sizeof(float);
     }
     P.items = xcd_order_items(work, NeqItemDev{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0}, /*by_default=*/false);
@@ -692,7 +608,7 @@ extern "C" int pleas_normal_eq_accum(const pleas_neq_layer* layers, int n_layers
         PLEAS_LAUNCH_CHECK("neq_set_ptrs_kernel");
     }
     ProfScope prof(kProfNormalEq, P.flops, P.bytes, stream);
-    hipLaunchKernelGGL(neq_batch_kernel, dim3((unsigned)P.items.size()), dim3(nThreads), P.lds, stream, dl,
+    hipLaunchKernelGGL(neq_batch_kernel, dim3((unsigned)P.items.size()), dim3(kThreads), P.lds, stream, dl,
                        reinterpret_cast<const NeqItemDev*>(base + P.off_items));
     PLEAS_LAUNCH_CHECK("neq_batch_kernel");
     if (!P.red.empty()) {

@@ -187,8 +187,8 @@ def test_merge_blocks_one_axis_activation(ops):
 
 
 @pytest.mark.parametrize("shape,axis", [((16, 256, 14, 14), 1), ((2, 64, 28, 28), 1), ((5, 132, 6, 6), 1), ((2, 64, 112, 112), 1)])
-def test_gram_split_bf16_study_switch(ops, shape, axis):
-    """The STUDY arithmetic of the contraction (three-way bf16 split, six bf16 MFMAs per fp32 product; off by default,
+def test_gram_split_bf16_switch(ops, shape, axis):
+    """The split-bf16 arithmetic of the contraction (three-way bf16 split, six bf16 MFMAs per fp32 product; off by default,
     DESIGN.md): within the exact path's own distance from fp64 (x2 + a floor) on 16-byte-loadable shapes, and the switch
     really goes back to the exact path (bit-identical results before and after)."""
     from pleas_merging_amd import _lib
@@ -200,11 +200,11 @@ def test_gram_split_bf16_study_switch(ops, shape, axis):
     want = orc.cross_features_inner_product(x.double(), y.double(), axis)
     exact = ops.cross_features_inner_product(xd, yd, axis).cpu()
     try:
-        _lib.lib().pleas_gram_split_bf16(1)
+        _lib.lib().pleas_arith(1)      # PLEAS_ARITH_SPLIT_BF16
         study = ops.cross_features_inner_product(xd, yd, axis).cpu()
         study_d = ops.cross_features_cdist(xd, yd, axis).cpu()
     finally:
-        _lib.lib().pleas_gram_split_bf16(0)
+        _lib.lib().pleas_arith(0)      # PLEAS_ARITH_FP32
     assert not torch.equal(study, exact)          # another arithmetic did run
     assert _rel(study, want) < max(2 * _rel(exact, want), 5e-7), (_rel(study, want), _rel(exact, want))
     assert _rel(study_d, orc.cross_features_cdist_f64(x, y, axis)) < 2e-6
@@ -694,6 +694,7 @@ NEQ_CASES = [
     (2, 32, 56, 56, 3, 1, 1),      # lag classes through slabs + reduce (196 chunks of the pixel axis)
     (5, 24, 8, 8, 5, 1, 2),        # 5x5 "same": 157 of 325 blocks contracted
     (2, 20, 2, 3, 3, 1, 1),        # image smaller than the kernel: empty windows
+    (2, 24, 9, 9, 3, 2, 1),        # stride 2 with Cin <= 64: the shifted loader on a ragged 64-tile, HWo = 25 scalar loads
 ]
 
 

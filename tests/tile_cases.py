@@ -13,7 +13,7 @@ import contextlib
 import ctypes
 
 F_TN = 128          # pixels per forward tile (fTN)
-W_BK = 32           # pixels per weight-gradient chunk (cBK)
+W_BK = 32           # pixels per weight-gradient chunk (kBK)
 
 # ------------------------------------------------------------------------------------------------ forward
 FWD_CASES = [
