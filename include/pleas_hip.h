@@ -425,6 +425,7 @@ int pleas_normal_eq_plan_info(const pleas_neq_layer* layers, int n_layers, doubl
  * solution.  A_p: K_p x K_p row-major, LOWER triangle read; overwritten (L below the diagonal, L^T
  * above).  A, Bt, K, N: HOST arrays (of DEVICE pointers / sizes); info: DEVICE int[nprob], 0 = ok,
  * j > 0 = pivot j not positive in fp32 (the caller should redo that problem in higher precision).
+ * N_p = 0 factors A_p only (Bt_p may then be null).
  * Problems of different sizes share the launches: cost = 5 * max(K)/64 launches per 96 problems.
  */
 int pleas_cholesky_solve_batched(float* const* A, float* const* Bt, const int* K, const int* N, int nprob, float lambda,

@@ -232,7 +232,8 @@ extern "C" int pleas_cholesky_solve_batched(float* const* A, float* const* Bt, c
     if (nprob == 0) return PLEAS_OK;
     if (!A || !Bt || !K || !N || !info) return bad_arg("cholesky_solve: null array");
     for (int p = 0; p < nprob; ++p)
-        if (!A[p] || !Bt[p] || K[p] <= 0 || N[p] < 0) return bad_arg("cholesky_solve: bad problem");
+        // N = 0 (factor only) has no right-hand side to point at: an empty tensor's address is null
+        if (!A[p] || K[p] <= 0 || N[p] < 0 || (!Bt[p] && N[p] > 0)) return bad_arg("cholesky_solve: bad problem");
     hipStream_t stream = (hipStream_t)stream_;
     PLEAS_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int) * (size_t)nprob, stream));
     double flops = 0;
@@ -241,11 +242,10 @@ extern "C" int pleas_cholesky_solve_batched(float* const* A, float* const* Bt, c
     for (int g0 = 0; g0 < nprob; g0 += sMaxProb) {
         SolveBatch b;
         b.count = std::min(sMaxProb, nprob - g0);
-        int Kmax = 0, rows_max = 0;
+        int Kmax = 0;
         for (int q = 0; q < b.count; ++q) {
             b.p[q] = SolveProb{A[g0 + q], Bt[g0 + q], K[g0 + q], N[g0 + q]};
             Kmax = std::max(Kmax, K[g0 + q]);
-            rows_max = std::max(rows_max, K[g0 + q] + N[g0 + q]);
         }
         if (lambda > 0.f) {
             hipLaunchKernelGGL(ridge_kernel, dim3(b.count), dim3(256), 0, stream, b, lambda);
@@ -253,12 +253,19 @@ extern "C" int pleas_cholesky_solve_batched(float* const* A, float* const* Bt, c
         }
         for (int j0 = 0; j0 < Kmax; j0 += sNB) {  // factorisation + forward substitution
             hipLaunchKernelGGL(potrf_diag_kernel, dim3(b.count), dim3(256), 0, stream, b, j0, info, g0);
-            const int nbmax = std::min(sNB, Kmax - j0);
-            const int rows = rows_max - j0 - nbmax;  // rows below the diagonal block (A rows + RHS rows)
+            // Every problem tiles from ITS OWN panel edge j0 + nb (nb < 64 in its last panel), so the grids are the most any
+            // still-active problem needs there: rows below its diagonal block (A rows + RHS rows), columns right of it.
+            int rows = 0, cols = 0;
+            for (int q = 0; q < b.count; ++q) {
+                const SolveProb& P = b.p[q];
+                if (j0 >= P.K) continue;
+                const int edge = j0 + std::min(sNB, P.K - j0);
+                rows = std::max(rows, P.K + P.N - edge);
+                cols = std::max(cols, P.K - edge);
+            }
             if (rows > 0) {
                 hipLaunchKernelGGL((trsm_rows_kernel<false>), dim3((unsigned)ceil_div(rows, 64), b.count), dim3(64), 0, stream,
                                    b, j0);
-                const int cols = Kmax - j0 - nbmax;
                 if (cols > 0)
                     hipLaunchKernelGGL((trail_update_kernel<false>),
                                        dim3((unsigned)ceil_div(cols, 128), (unsigned)ceil_div(rows, 128), b.count), dim3(256),

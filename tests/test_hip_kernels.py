@@ -695,19 +695,22 @@ NEQ_CASES = [
     (5, 24, 8, 8, 5, 1, 2),        # 5x5 "same": 157 of 325 blocks contracted
     (2, 20, 2, 3, 3, 1, 1),        # image smaller than the kernel: empty windows
     (2, 24, 9, 9, 3, 2, 1),        # stride 2 with Cin <= 64: the shifted loader on a ragged 64-tile, HWo = 25 scalar loads
+    (2, 30, 6, 6, 3, 1, 1),        # lag classes, 16-byte pixel loads, Cin % 4 != 0: the scalar epilogue under the 64-tile
+    (2, 70, 4, 6, 3, 1, 1),        # the same under the 128-tile
 ]
 
 
-@pytest.mark.parametrize("N,Cin,H,W,k,stride,pad", NEQ_CASES)
-def test_normal_eq_accum_matches_unfold(ops, N, Cin, H, W, k, stride, pad):
+def _neq_accumulate(ops, case, A, reps=2):
+    """``reps`` batches accumulated into ``A`` (zeroed here), finalized twice; returns U^T U of the same batches in fp64."""
     import torch.nn.functional as F
 
+    N, Cin, H, W, k, stride, pad = case
     g = torch.Generator().manual_seed(N + Cin + k)
     K = k * k * Cin
-    A = torch.zeros(K, K, device="cuda")
+    A.zero_()
     batch = ops.NormalEqBatch(torch.device("cuda"))
     want = torch.zeros(K, K, dtype=torch.float64)
-    for rep in range(2):  # accumulates over batches
+    for rep in range(reps):  # accumulates over batches
         ip = torch.randn(N, Cin, H, W, generator=g)
         U = F.unfold(ip.double(), k, 1, pad, stride)                                   # N, (ci, r), L
         U = U.view(N, Cin, k * k, -1).permute(0, 3, 2, 1).reshape(-1, K)               # rows x (r, ci)
@@ -719,7 +722,14 @@ def test_normal_eq_accum_matches_unfold(ops, N, Cin, H, W, k, stride, pad):
     assert info["blocks_to_finalize"] == ({3: 16, 5: 168}[k] if lag else 0)
     batch.finalize()                  # copies / transposes of the contracted lag-class blocks (once, after the last batch)
     batch.finalize()                  # idempotent
-    got = A.cpu().double()
+    return want
+
+
+def _neq_check(case, got, want):
+    """The lower block tiles against fp64 as a whole and, for a lag-form layer, kernel-position block by block (a wrong
+    class copy in pleas_normal_eq_finalize points at its block); the strict upper tiles untouched."""
+    N, Cin, H, W, k, stride, pad = case
+    K = k * k * Cin
     T = 128 if Cin > 64 else 64
     tiles = -(-Cin // T)
     blk = lambda idx: (idx // Cin) * tiles + (idx % Cin) // T                      # block-tile index of a row/col
@@ -727,6 +737,41 @@ def test_normal_eq_accum_matches_unfold(ops, N, Cin, H, W, k, stride, pad):
     lower = blk(rows)[:, None] >= blk(rows)[None, :]
     assert _rel(got[lower], want[lower]) < 3e-6
     assert (got[~lower] == 0).all()                                                    # strict upper tiles untouched
+    if k > 1 and stride == 1 and 2 * pad == k - 1:
+        checked = 0
+        for rx in range(k * k):
+            for ry in range(rx + 1):
+                sl = (slice(rx * Cin, (rx + 1) * Cin), slice(ry * Cin, (ry + 1) * Cin))
+                m = lower[sl]
+                assert _rel(got[sl][m], want[sl][m]) < 3e-6, (rx, ry, _rel(got[sl][m], want[sl][m]))
+                checked += 1
+        assert checked == k * k * (k * k + 1) // 2
+
+
+@pytest.mark.parametrize("N,Cin,H,W,k,stride,pad", NEQ_CASES)
+def test_normal_eq_accum_matches_unfold(ops, N, Cin, H, W, k, stride, pad):
+    case = (N, Cin, H, W, k, stride, pad)
+    K = k * k * Cin
+    A = torch.zeros(K, K, device="cuda")
+    want = _neq_accumulate(ops, case, A)
+    _neq_check(case, A.cpu().double(), want)
+
+
+@pytest.mark.parametrize("case", [(4, 64, 14, 14, 1, 1, 0), (4, 48, 10, 10, 3, 1, 1)], ids=["direct", "lag"])
+def test_normal_eq_accum_A_not_16_byte_aligned(ops, case):
+    """The fitter's A matrices are views of one arena: 4-byte aligned, not necessarily 16.  Cin % 4 == 0 here, so the
+    aligned run takes the epilogue's 16-byte read-modify-writes and the view one float further on the scalar ones.
+    NormalEqBatch.add accepts such a view (it asks for contiguity and shape only)."""
+    K = case[4] * case[4] * case[1]
+    aligned = torch.zeros(K, K, device="cuda")
+    arena = torch.zeros(K * K + 8, device="cuda")
+    view = arena[1:1 + K * K].view(K, K)
+    assert aligned.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 and view.is_contiguous()
+    want = _neq_accumulate(ops, case, aligned)
+    _neq_accumulate(ops, case, view)
+    assert torch.equal(view, aligned)
+    _neq_check(case, view.cpu().double(), want)
+    assert float(arena[0]) == 0.0 and (arena[1 + K * K:] == 0).all()                   # nothing written around the view
 
 
 def test_wgrad_accumulate_kpos_major(ops):
