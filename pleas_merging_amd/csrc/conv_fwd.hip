@@ -12,13 +12,14 @@
 //
 // Formulation: implicit GEMM  out[co][P] = sum_k W[co][k] * U[k][P],  P = (n, oh, ow) flattened,
 // k = (ci, kh, kw) in the standard weight order.  A workgroup owns TM output channels x 128 pixels;
-// W rows are K-contiguous (A operand, 16-B LDS reads feeding four MFMA steps, as in gram.hip);
+// W rows are K-contiguous (A operand, 16-B LDS reads feeding four MFMA steps: the NT core of nt_tile.hpp);
 // U is read in place from the NCHW input: a thread owns ONE pixel for the whole K loop (its (n, oh, ow)
 // is decoded once) and walks (ci, kh, kw) incrementally, so consecutive lanes read consecutive
 // addresses for stride-1 layers; its 16 values of a chunk are one contiguous run of the [pixel][k] LDS
 // tile (four 16-B stores), so BOTH operands are read back with the 16-B / four-MFMA-step pattern of
-// gram.hip.  The epilogue goes through LDS once to turn the accumulator layout (one pixel per lane)
-// into 16-B runs along the pixel axis for the target gathers and the residual stores.
+// nt_mma_fp32 (the flat forms below hand the core's exact step their own B sources).  The epilogue goes
+// through LDS once to turn the accumulator layout (one pixel per lane) into 16-B runs along the pixel
+// axis for the target gathers and the residual stores.
 // Items of all layers are sorted longest-first into one grid.
 //
 // Work: 2*Cout*Cin*KH*KW*N*HWo flop per layer (same as the weight gradient), fp32-MFMA bound.
@@ -26,19 +27,16 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
 #include "fwd_schedule.hpp"
+#include "nt_tile.hpp"
 
 namespace pleas {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short s16x4_t __attribute__((ext_vector_type(4)));   // what ds_read_tr16_b64 returns
+typedef short s16x8_t __attribute__((ext_vector_type(8)));
 
-constexpr int fBK = 32;
-constexpr int fLdsA = 36;    // W tile rows: [TM][36]   (k contiguous)
-constexpr int fLdsB = 36;    // U tile rows: [128 pixels][36] (k contiguous: a thread's 16 k values of its pixel are one run)
+// W tile rows: [TM][kLds] (k contiguous); U tile rows: [fTN pixels][kLds] (k contiguous: a thread's 16 k values of its pixel are one run)
 constexpr int fTN = 128;
-constexpr int fThreads = 256;
 
 struct FwdLayerDev {
     const float* ip;      // merged input  [N][Cin][Hin][Win]
@@ -68,24 +66,35 @@ struct FwdItemDev {
     int layer, tm, tp, slot;  // slot: loss-partial index
 };
 
-// ---- shared by both tile forms: the block maps / biases of a tile's output channels, and the epilogue
+// ---- shared by both tile forms: the epilogue and its per-row operands.  A thread owns the TM / 8 output channels
+// tid / 32 + 8 j of its tile; per channel the epilogue takes two 32-bit values and the bias:
+//   PLAIN 0 / 1: the channel's rows in the two sources' outputs (the block maps; -1 = absent)
+//   PLAIN 2:     the channel's BatchNorm scale and shift (no block maps there)
+template <int TM, int PLAIN>
+struct FwdRowOps {
+    int row1[TM / 8], row2[TM / 8];
+    float bias[TM / 8];
+};
+template <int TM>
+struct FwdRowOps<TM, 2> {
+    float scale[TM / 8], shift[TM / 8];
+    float bias[TM / 8];
+};
 template <int TM, int PLAIN = 0>
-__device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0, int (&m1)[TM / 8], int (&m2)[TM / 8],
-                                              float (&bias_v)[TM / 8]) {
+__device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0, FwdRowOps<TM, PLAIN>& ops) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int j = 0; j < TM / 8; ++j) {
         const int co = min(i0 + (tid >> 5) + 8 * j, L.Cout - 1);
-        if constexpr (PLAIN == 2) {      // no block maps: their registers carry the channel's affine map (as bit patterns)
-            m1[j] = __float_as_int(PLEAS_GLOBAL(L.bn_scale)[co]);
-            m2[j] = __float_as_int(PLEAS_GLOBAL(L.bn_shift)[co]);
-            bias_v[j] = L.bias ? PLEAS_GLOBAL(L.bias)[co] : 0.f;
-            continue;
+        if constexpr (PLAIN == 2) {
+            ops.scale[j] = PLEAS_GLOBAL(L.bn_scale)[co];
+            ops.shift[j] = PLEAS_GLOBAL(L.bn_shift)[co];
+        } else {
+            // a plain convolution (pleas_conv2d_fwd) has no block maps: every source row is absent, the target is zero
+            ops.row1[j] = L.row1 ? PLEAS_GLOBAL_I(L.row1)[co] : -1;
+            ops.row2[j] = L.row2 ? PLEAS_GLOBAL_I(L.row2)[co] : -1;
         }
-        // a plain convolution (pleas_conv2d_fwd) has no block maps: every source row is absent, the target is zero
-        m1[j] = L.row1 ? PLEAS_GLOBAL_I(L.row1)[co] : -1;
-        m2[j] = L.row2 ? PLEAS_GLOBAL_I(L.row2)[co] : -1;
-        bias_v[j] = L.bias ? PLEAS_GLOBAL(L.bias)[co] : 0.f;
+        ops.bias[j] = L.bias ? PLEAS_GLOBAL(L.bias)[co] : 0.f;
     }
 }
 
@@ -95,8 +104,7 @@ __device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0
 // the gather slots of the target
 template <int TM, int PLAIN = 0>
 __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItemDev& it, f32x16 (&acc)[TM / 64][2],
-                                             const int (&m1)[TM / 8], const int (&m2)[TM / 8],
-                                             const float (&bias_v)[TM / 8], float* smem, float* __restrict__ partials) {
+                                             const FwdRowOps<TM, PLAIN>& ops, float* smem, float* __restrict__ partials) {
     constexpr int MTM = TM / 64;
     constexpr int ROWS = TM / 8, GB = 8, NB = ROWS / GB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -147,8 +155,6 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
 #pragma unroll
             for (int u = 0; u < GB; ++u) {
                 const int j = bt * GB + u;
-                const uint32_t oa = (gin && m1[j] >= 0) ? gbase + (uint32_t)m1[j] * hw4 : 0u;
-                const uint32_t ob = (gin && m2[j] >= 0) ? gbase + (uint32_t)m2[j] * hw4 : 0u;
                 if constexpr (PLAIN == 2) {
                     // unconditional load from a valid address (the output's own offset into the identity; the first floats
                     // of the input for rows / pixels outside the layer and when there is no identity -- then voided by a
@@ -160,6 +166,8 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 } else if constexpr (PLAIN) {
                     ta[bt][u] = tb[bt][u] = f32x4{0.f, 0.f, 0.f, 0.f};
                 } else {
+                    const uint32_t oa = (gin && ops.row1[j] >= 0) ? gbase + (uint32_t)ops.row1[j] * hw4 : 0u;
+                    const uint32_t ob = (gin && ops.row2[j] >= 0) ? gbase + (uint32_t)ops.row2[j] * hw4 : 0u;
                     ta[bt][u] = *(const __attribute__((address_space(1))) f32x4*)(o1b + oa);
                     tb[bt][u] = *(const __attribute__((address_space(1))) f32x4*)(o2b + ob);
                 }
@@ -172,36 +180,35 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const int lco = (tid >> 5) + 8 * j, co = i0 + lco;
                 const bool live = gin && co < L.Cout;
                 if constexpr (PLAIN == 2) {
-                    const float a = __int_as_float(m1[j]), b = __int_as_float(m2[j]);
                     const f32x4 o = *reinterpret_cast<const f32x4*>(Ct + lco * EL + pg);
                     f32x4 y, z;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        y[e] = o[e] + bias_v[j];
-                        const float sm = fmaf(y[e], a, b) + ta[bt][u][e];
+                        y[e] = o[e] + ops.bias[j];
+                        const float sm = fmaf(y[e], ops.scale[j], ops.shift[j]) + ta[bt][u][e];
                         z[e] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
                     }
                     if (live) {
                         *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = y;
                         *(__attribute__((address_space(1))) f32x4*)(zb_ + (rbase + (uint32_t)(8 * j) * hw4)) = z;
                     }
-                    continue;
-                }
-                // target = (o1 * [present] + o2 * [present]) * coef, coef in {0.5, 1}: folding coef into the two factors is
-                // exact (power of two), so  fma(o2, cb, o1 * ca)  rounds once, like the sum it replaces
-                const float coef = co < L.n_merged ? 0.5f : 1.0f;
-                const float ca = m1[j] >= 0 ? coef : 0.f, cb = m2[j] >= 0 ? coef : 0.f;
-                const f32x4 o = *reinterpret_cast<const f32x4*>(Ct + lco * EL + pg);
-                f32x4 d;
-                float s4 = 0.f;
+                } else {
+                    // target = (o1 * [present] + o2 * [present]) * coef, coef in {0.5, 1}: folding coef into the two factors is
+                    // exact (power of two), so  fma(o2, cb, o1 * ca)  rounds once, like the sum it replaces
+                    const float coef = co < L.n_merged ? 0.5f : 1.0f;
+                    const float ca = ops.row1[j] >= 0 ? coef : 0.f, cb = ops.row2[j] >= 0 ? coef : 0.f;
+                    const f32x4 o = *reinterpret_cast<const f32x4*>(Ct + lco * EL + pg);
+                    f32x4 d;
+                    float s4 = 0.f;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float dd = (o[e] + bias_v[j]) - fmaf(tb[bt][u][e], cb, ta[bt][u][e] * ca);
-                    s4 = fmaf(dd, dd, s4);
-                    d[e] = L.dscale * dd;
+                    for (int e = 0; e < 4; ++e) {
+                        const float dd = (o[e] + ops.bias[j]) - fmaf(tb[bt][u][e], cb, ta[bt][u][e] * ca);
+                        s4 = fmaf(dd, dd, s4);
+                        d[e] = L.dscale * dd;
+                    }
+                    sq += live ? s4 : 0.f;
+                    if (live) *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = d;
                 }
-                sq += live ? s4 : 0.f;
-                if (live) *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = d;
             }
         };
         gather(0);
@@ -224,18 +231,18 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const uint32_t n = Pe / L.HWo, p = Pe - n * L.HWo;
                 if constexpr (PLAIN == 2) {
                     const size_t at = ((size_t)n * L.Cout + co) * L.HWo + p;
-                    const float y = o[e] + bias_v[j];
-                    const float sm = fmaf(y, __int_as_float(m1[j]), __int_as_float(m2[j])) + (L.bn_res ? PLEAS_GLOBAL(L.bn_res)[at] : 0.f);
+                    const float y = o[e] + ops.bias[j];
+                    const float sm = fmaf(y, ops.scale[j], ops.shift[j]) + (L.bn_res ? PLEAS_GLOBAL(L.bn_res)[at] : 0.f);
                     PLEAS_GLOBAL_W(L.resid)[at] = y;
                     PLEAS_GLOBAL_W(L.bn_z)[at] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
-                    continue;
+                } else {
+                    float a = 0.f, b = 0.f;
+                    if (ops.row1[j] >= 0) a = PLEAS_GLOBAL(L.o1)[((size_t)n * L.Csrc + ops.row1[j]) * L.HWo + p];
+                    if (ops.row2[j] >= 0) b = PLEAS_GLOBAL(L.o2)[((size_t)n * L.Csrc + ops.row2[j]) * L.HWo + p];
+                    const float dd = (o[e] + ops.bias[j]) - (a + b) * coef;
+                    sq = fmaf(dd, dd, sq);
+                    PLEAS_GLOBAL_W(L.resid)[((size_t)n * L.Cout + co) * L.HWo + p] = L.dscale * dd;
                 }
-                float a = 0.f, b = 0.f;
-                if (m1[j] >= 0) a = PLEAS_GLOBAL(L.o1)[((size_t)n * L.Csrc + m1[j]) * L.HWo + p];
-                if (m2[j] >= 0) b = PLEAS_GLOBAL(L.o2)[((size_t)n * L.Csrc + m2[j]) * L.HWo + p];
-                const float dd = (o[e] + bias_v[j]) - (a + b) * coef;
-                sq = fmaf(dd, dd, sq);
-                PLEAS_GLOBAL_W(L.resid)[((size_t)n * L.Cout + co) * L.HWo + p] = L.dscale * dd;
             }
         }
     }
@@ -247,32 +254,47 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
     if (tid == 0 && partials) partials[L.part_base + it.slot] = (smem[0] + smem[1]) + (smem[2] + smem[3]);
 }
 
+// The weight rows a thread stages per chunk, for both tile forms: LPR lanes share a row's 32 k (VEC floats each), the 256 threads
+// cover RPP rows per pass and the tile's TM rows in PASS passes.  SPLIT_ROWS: the rows of a pass are permuted so that the split
+// planes are written without bank conflicts (split_stage_row, common.hpp).
+template <int TM, int VEC, bool SPLIT_ROWS = false>
+struct FwdWeightRows {
+    static constexpr int LPR = kBK / VEC, RPP = kThreads / LPR, PASS = TM / RPP;
+    int arow, acol;           // first row of this thread in the tile, its k offset in the chunk
+    unsigned oka = 0;         // bit q: row arow + q * RPP is a channel of the layer
+    uint32_t offa[PASS];      // where that row starts in W (clamped to the last channel: loads stay in bounds, oka masks them)
+    __device__ __forceinline__ FwdWeightRows(const FwdLayerDev& L, const int i0) {
+        const int tid = threadIdx.x;
+        arow = SPLIT_ROWS ? split_stage_row(tid / LPR) : tid / LPR;
+        acol = (tid % LPR) * VEC;
+#pragma unroll
+        for (int q = 0; q < PASS; ++q) {
+            const int gi = i0 + arow + q * RPP;
+            if (gi < L.Cout) oka |= 1u << q;
+            offa[q] = (uint32_t)min(gi, L.Cout - 1) * L.Kd;
+        }
+    }
+};
+
 template <int TM, int VECA, int PLAIN = 0>
 __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev& it, float* smem, float* __restrict__ partials) {
     constexpr int MTM = TM / 64;
-    constexpr int LPR = fBK / VECA, RPP = fThreads / LPR, PASS = TM / RPP;
-    float* As = smem;                      // [2][TM][fLdsA]
-    float* Bs = smem + 2 * TM * fLdsA;     // [2][fTN][fLdsB]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    using WRows = FwdWeightRows<TM, VECA>;
+    constexpr int RPP = WRows::RPP, PASS = WRows::PASS;
+    float* As = smem;                      // [2][TM][kLds]
+    float* Bs = smem + 2 * TM * kLds;      // [2][fTN][kLds]
+    const int tid = threadIdx.x;
     const int i0 = it.tm * TM;
     const uint32_t p0 = (uint32_t)it.tp * fTN;
     const uint32_t HWi = (uint32_t)L.Hin * L.Win;
     const int R = L.KH * L.KW;
     const bool kpos = (L.variant & 4) != 0;
-    const int nchunks = (int)((L.Kd + fBK - 1) / fBK);
+    const int nchunks = (int)((L.Kd + kBK - 1) / kBK);
 
     // ---- A (weights) staging: rows co, k contiguous
-    const int arow = tid / LPR, acol = (tid % LPR) * VECA;
+    const WRows wr(L, i0);
+    const int arow = wr.arow, acol = wr.acol;
     float ra[PASS][VECA];
-    unsigned oka = 0;
-    uint32_t offa[PASS];
-#pragma unroll
-    for (int q = 0; q < PASS; ++q) {
-        const int gi = i0 + arow + q * RPP;
-        if (gi < L.Cout) oka |= 1u << q;
-        offa[q] = (uint32_t)min(gi, L.Cout - 1) * L.Kd;
-    }
     // ---- B (input) staging: this thread's pixel and half of the chunk's k rows
     const int bpix = tid & 127;
     const int bhalf = __builtin_amdgcn_readfirstlane(tid >> 7);  // wave-uniform: the k walk below stays on the scalar unit
@@ -295,28 +317,23 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
     }
 
     f32x16 acc[MTM][2];
-#pragma unroll
-    for (int a = 0; a < MTM; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    nt_zero(acc);
 
     auto load_chunk = [&](int c) {
         {
             // kernel-position-major weights: chunk c = (channel block c / R, tap c % R); its 32 k values sit at
             // [tap][block * 32 ..] of the weight row
-            const uint32_t k = kpos ? (uint32_t)(c % R) * L.Cin + (uint32_t)(c / R) * fBK + acol : (uint32_t)c * fBK + acol;
+            const uint32_t k = kpos ? (uint32_t)(c % R) * L.Cin + (uint32_t)(c / R) * kBK + acol : (uint32_t)c * kBK + acol;
             kina = k < L.Kd;
             const uint32_t kc = kina ? k : 0u;
 #pragma unroll
             for (int q = 0; q < PASS; ++q) {
                 if constexpr (VECA == 4) {
-                    const f32x4 v = *(const __attribute__((address_space(1))) f32x4*)(PLEAS_GLOBAL(L.w) + offa[q] + kc);
+                    const f32x4 v = *(const __attribute__((address_space(1))) f32x4*)(PLEAS_GLOBAL(L.w) + wr.offa[q] + kc);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ra[q][e] = v[e];
                 } else {
-                    ra[q][0] = PLEAS_GLOBAL(L.w)[offa[q] + kc];
+                    ra[q][0] = PLEAS_GLOBAL(L.w)[wr.offa[q] + kc];
                 }
             }
         }
@@ -324,7 +341,7 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
             // Every lane of a wave walks the SAME k values (wave-uniform ci, kh, kw); only the pixel differs.
             // Loads are unconditional: an out-of-range tap reads element 0 (offset masked to zero, no branch) and is
             // zeroed when the tile is written to LDS.
-            const uint32_t k = (uint32_t)c * fBK + bhalf * 16;
+            const uint32_t k = (uint32_t)c * kBK + bhalf * 16;
             okb = 0;
             if (R == 1 || kpos) {
                 // ONE tap per chunk (1x1 / Linear, or kernel-position-major weights: channel block c / R, tap c % R; the
@@ -334,7 +351,7 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
                 const int r = kpos ? c - cb * R : 0;
                 const int kh = r / L.KW, kw = r - kh * L.KW;
                 const bool ok_tap = (tapmask >> r) & 1ull;
-                const uint32_t ch0 = (uint32_t)cb * fBK + bhalf * 16;
+                const uint32_t ch0 = (uint32_t)cb * kBK + bhalf * 16;
                 const long long voff = ok_tap ? (long long)pbase + pixoff + (kh * L.Win + kw) : 0ll;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
@@ -371,17 +388,17 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
         }
     };
     auto store_chunk = [&](int buf) {
-        float* a = As + buf * TM * fLdsA;
-        float* b = Bs + buf * fTN * fLdsB;
+        float* a = As + buf * TM * kLds;
+        float* b = Bs + buf * fTN * kLds;
 #pragma unroll
         for (int q = 0; q < PASS; ++q) {
-            const bool ok = kina && ((oka >> q) & 1u);
+            const bool ok = kina && ((wr.oka >> q) & 1u);
             const int row = arow + q * RPP;
             if constexpr (VECA == 4) {
                 f32x4 v = {ok ? ra[q][0] : 0.f, ok ? ra[q][1] : 0.f, ok ? ra[q][2] : 0.f, ok ? ra[q][3] : 0.f};
-                *reinterpret_cast<f32x4*>(a + row * fLdsA + acol) = v;
+                *reinterpret_cast<f32x4*>(a + row * kLds + acol) = v;
             } else {
-                a[row * fLdsA + acol] = ok ? ra[q][0] : 0.f;
+                a[row * kLds + acol] = ok ? ra[q][0] : 0.f;
             }
         }
 #pragma unroll
@@ -389,38 +406,19 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
             f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = ((okb >> (q4 * 4 + e)) & 1u) ? rb[q4 * 4 + e] : 0.f;
-            *reinterpret_cast<f32x4*>(b + bpix * fLdsB + bhalf * 16 + q4 * 4) = v;
+            *reinterpret_cast<f32x4*>(b + bpix * kLds + bhalf * 16 + q4 * 4) = v;
         }
     };
-    auto compute = [&](int buf) {
-        const float* a = As + buf * TM * fLdsA + (wm * (TM / 2) + (lane & 31)) * fLdsA + 4 * (lane >> 5);
-        const float* b = Bs + buf * fTN * fLdsB + (wn * 64 + (lane & 31)) * fLdsB + 4 * (lane >> 5);
-#pragma unroll
-        for (int kk = 0; kk < fBK / 8; ++kk) {
-            f32x4 fa[MTM], fb[2];
-#pragma unroll
-            for (int s = 0; s < MTM; ++s) fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * fLdsA + kk * 8);
-#pragma unroll
-            for (int s = 0; s < 2; ++s) fb[s] = *reinterpret_cast<const f32x4*>(b + s * 32 * fLdsB + kk * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int sm = 0; sm < MTM; ++sm)
-#pragma unroll
-                    for (int sn = 0; sn < 2; ++sn)
-                        acc[sm][sn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], fb[sn][e], acc[sm][sn], 0, 0, 0);
-        }
-    };
+    auto compute = [&](int buf) { nt_mma_fp32<TM, fTN>(As, Bs, buf, acc); };
 
+    // nt_pipeline<0>'s order with the last chunk taken out of the loop: the block maps and biases of the epilogue are requested
+    // before the LAST chunk's MFMAs (no staging loads are in flight then), so that their round trip is covered by that chunk
+    // instead of opening the epilogue.  (Requested from nt_pipeline's compute callback they are live across its loop: the 128-row
+    // forms then spill 164-320 B per lane.)
     load_chunk(0);
     store_chunk(0);
     __syncthreads();
-    // The block maps and biases of the epilogue are requested before the LAST chunk's MFMAs (no staging loads are in
-    // flight then): their round trip is covered by that chunk instead of opening the epilogue.
-    constexpr int ROWS = TM / 8;
-    int m1[ROWS], m2[ROWS];
-    float bias_v[ROWS];
-    auto load_maps = [&]() { fwd_load_maps<TM, PLAIN>(L, i0, m1, m2, bias_v); };
+    FwdRowOps<TM, PLAIN> ops;
     for (int c = 0; c + 1 < nchunks; ++c) {
         const int buf = c & 1;
         load_chunk(c + 1);
@@ -428,11 +426,11 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
         store_chunk(buf ^ 1);
         __syncthreads();
     }
-    load_maps();
+    fwd_load_maps<TM, PLAIN>(L, i0, ops);
     compute((nchunks - 1) & 1);
     __syncthreads();
 
-    fwd_epilogue<TM, PLAIN>(L, it, acc, m1, m2, bias_v, smem, partials);
+    fwd_epilogue<TM, PLAIN>(L, it, acc, ops, smem, partials);
 }
 
 
@@ -464,12 +462,12 @@ constexpr int fFlatColsK = 248;    // columns of that image: 128 + 2 * halo data
 //                 ds_read_b64_tr_b16 -- the hardware transposes 4 k x 16 pixels per 16-lane group
 constexpr int fSplitPixRow = 160;  // bf16 per k row of the 1 x 1 split image: 128 pixels + 32 pad = 320 B (rows 16 banks apart:
                                    // the four rows x eight 8-byte column chunks of a half-wave's transposed read hit 32 distinct bank pairs)
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
 template <int TM, int KIND, int SPLIT = 0, int PLAIN = 0>
 __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdItemDev& it, float* smem, float* __restrict__ partials) {
     static_assert(!SPLIT || KIND != 1, "the scalar 1 x 1 form (7 x 7 images) has no split variant");
     constexpr int MTM = TM / 64;
-    constexpr int LPR = fBK / 4, RPP = fThreads / LPR, PASS = TM / RPP;   // weight staging: 16-B loads
+    using WRows = FwdWeightRows<TM, 4, SPLIT != 0>;                      // weight staging: 16-B loads
+    constexpr int RPP = WRows::RPP, PASS = WRows::PASS;
     constexpr int Lr = KIND == 2 ? fFlatPix : fFlatRow1;                // compile-time: LDS offsets are immediates
     constexpr int jz = KIND == 2 ? fFlatColsK - 1 : Lr - 1;              // the zero column (k x k: the zero ROW of the image)
     constexpr int NBUF = KIND == 2 ? 1 : 2;
@@ -483,24 +481,17 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
     const uint32_t HW = L.HWo;                       // == Hin * Win
     const int halo = KIND == 2 ? L.pad * (W + 1) : 0;
     const int span = fTN + 2 * halo;                 // data columns of a Bs row
-    const int CB = L.Cin / fBK;
+    const int CB = L.Cin / kBK;
     const int nchunks = CB * R;
-    float* As = smem;                                // [2][TM][fLdsA]
-    float* Bs = smem + 2 * TM * fLdsA;               // 1x1: [NBUF][32][Lr]; k x k: [fFlatColsK][fFlatPix]
+    float* As = smem;                                // [2][TM][kLds]
+    float* Bs = smem + 2 * TM * kLds;                // 1x1: [NBUF][32][Lr]; k x k: [fFlatColsK][fFlatPix]
     __bf16* As16 = reinterpret_cast<__bf16*>(smem);  // SPLIT: [TM][kSplitRow]
     __bf16* Bs16 = As16 + TM * kSplitRow;            // SPLIT: k x k [fFlatColsK][kSplitRow]; 1 x 1 [3][32][fSplitPixRow]
 
     // ---- A (weights) staging, as in fwd_tile with VECA = 4
-    const int arow = SPLIT ? split_stage_row(tid / LPR) : tid / LPR, acol = (tid % LPR) * 4;      // SPLIT: conflict-free plane writes
+    const WRows wr(L, i0);
+    const int arow = wr.arow, acol = wr.acol;
     f32x4 ra0[PASS], ra1[PASS];    // two register sets: the weights of chunk c + 2 are requested while chunk c computes
-    unsigned oka = 0;
-    uint32_t offa[PASS];
-#pragma unroll
-    for (int q = 0; q < PASS; ++q) {
-        const int gi = i0 + arow + q * RPP;
-        if (gi < L.Cout) oka |= 1u << q;
-        offa[q] = (uint32_t)min(gi, L.Cout - 1) * L.Kd;
-    }
     // ---- B (input) staging.
     //   KIND 0: thread = (row tid / 32 + 8 i, pixel group tid % 32), i < 4: four 16-B loads per chunk
     //   else  : wave w owns rows 8 w .. 8 w + 7, lane covers columns lane + 64 m (columns >= span unused)
@@ -554,17 +545,12 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
     }
 
     f32x16 acc[MTM][2];
-#pragma unroll
-    for (int a = 0; a < MTM; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    nt_zero(acc);
 
     auto load_a = [&](int cb, int r, f32x4 (&ra)[PASS]) {
-        const uint32_t k = (uint32_t)r * L.Cin + (uint32_t)cb * fBK + acol;    // kernel-position-major (== plain for 1x1)
+        const uint32_t k = (uint32_t)r * L.Cin + (uint32_t)cb * kBK + acol;    // kernel-position-major (== plain for 1x1)
 #pragma unroll
-        for (int q = 0; q < PASS; ++q) ra[q] = *(const __attribute__((address_space(1))) f32x4*)(PLEAS_GLOBAL(L.w) + offa[q] + k);
+        for (int q = 0; q < PASS; ++q) ra[q] = *(const __attribute__((address_space(1))) f32x4*)(PLEAS_GLOBAL(L.w) + wr.offa[q] + k);
     };
     // Tiles whose rows / pixels all exist store their staged values as they are (block-uniform tests): every select that is
     // not executed is vector-pipe time the fp32 MFMAs get back (a vector instruction costs ~4.5 cycles of it).
@@ -574,27 +560,27 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
         if constexpr (SPLIT) {
 #pragma unroll
             for (int q = 0; q < PASS; ++q) {
-                const bool ok = full_a || ((oka >> q) & 1u);
+                const bool ok = full_a || ((wr.oka >> q) & 1u);
                 split3_store4(As16 + (arow + q * RPP) * kSplitRow, acol, ok ? ra[q][0] : 0.f, ok ? ra[q][1] : 0.f,
                               ok ? ra[q][2] : 0.f, ok ? ra[q][3] : 0.f);
             }
             return;
         }
-        float* a = As + buf * TM * fLdsA;
+        float* a = As + buf * TM * kLds;
         if (full_a) {
 #pragma unroll
-            for (int q = 0; q < PASS; ++q) *reinterpret_cast<f32x4*>(a + (arow + q * RPP) * fLdsA + acol) = ra[q];
+            for (int q = 0; q < PASS; ++q) *reinterpret_cast<f32x4*>(a + (arow + q * RPP) * kLds + acol) = ra[q];
             return;
         }
 #pragma unroll
         for (int q = 0; q < PASS; ++q) {
-            const bool ok = (oka >> q) & 1u;
+            const bool ok = (wr.oka >> q) & 1u;
             const f32x4 v = {ok ? ra[q][0] : 0.f, ok ? ra[q][1] : 0.f, ok ? ra[q][2] : 0.f, ok ? ra[q][3] : 0.f};
-            *reinterpret_cast<f32x4*>(a + (arow + q * RPP) * fLdsA + acol) = v;
+            *reinterpret_cast<f32x4*>(a + (arow + q * RPP) * kLds + acol) = v;
         }
     };
     auto load_b = [&](int cb, auto& rb) {
-        const cgfloat* base = PLEAS_GLOBAL(L.ip) + (size_t)cb * fBK * HW;
+        const cgfloat* base = PLEAS_GLOBAL(L.ip) + (size_t)cb * kBK * HW;
         if constexpr (KIND == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -621,7 +607,7 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
                 split3_pair(vok ? rb[4 * i + 2] : 0.f, vok ? rb[4 * i + 3] : 0.f, hi);
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
-                    *reinterpret_cast<u32x2_t*>(Bs16 + (p * fBK + (tid >> 5) + 8 * i) * fSplitPixRow + 4 * (tid & 31)) = u32x2_t{lo[p], hi[p]};
+                    *reinterpret_cast<u32x2_t*>(Bs16 + (p * kBK + (tid >> 5) + 8 * i) * fSplitPixRow + 4 * (tid & 31)) = u32x2_t{lo[p], hi[p]};
             }
             return;
         } else if constexpr (SPLIT && KIND == 2) {
@@ -641,7 +627,7 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
                 }
             return;
         }
-        float* b = Bs + buf * fBK * Lr;
+        float* b = Bs + buf * kBK * Lr;
         if constexpr (KIND == 0) {
             if (full_b) {
 #pragma unroll
@@ -687,24 +673,25 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
         while (rr >= L.KW) { rr -= L.KW; ++kh; }      // r < 32, KW >= 3: at most a few scalar steps
         return delta0 + kh * W + rr;
     };
+    // One chunk.  A lane whose tap (k x k) or pixel (1 x 1: past the tensor's end) is not there takes 0 by reading the image's zero
+    // row / the row's zero column: one select on the address per tap and fragment instead of one per value, made here, outside
+    // the k loops.  Exact: the core's step (nt_mma_fp32_from) with this form's B source.  Split: written out -- unlike
+    // nt_mma_split it reads all A fragments of a k group before the B fragments, and the 1 x 1 form's B fragments pixel fragment
+    // by pixel fragment; that order is kept.
     auto compute = [&](int abuf, int bbuf, int r) {
         const int delta = tap_delta(r);
-        const float* a = As + abuf * TM * fLdsA + (wm * (TM / 2) + (lane & 31)) * fLdsA + 4 * (lane >> 5);
-        const float* bb = Bs + bbuf * fBK * Lr + 4 * (lane >> 5) * Lr;     // half-wave h takes k = 8 kk + e + 4 h
-        // A lane whose tap (k x k) or pixel (1 x 1: past the tensor's end) is not there takes 0 by reading the image's zero
-        // row / the row's zero column: one select on the address per tap and fragment instead of one per value.
         const bool ok0 = (tapok[0] >> r) & 1u, ok1 = (tapok[1] >> r) & 1u;
         if constexpr (SPLIT) {
             const __bf16* a16 = As16 + (wm * (TM / 2) + (lane & 31)) * kSplitRow + 8 * (lane >> 5);
 #pragma unroll
-            for (int g16 = 0; g16 < fBK / 16; ++g16) {
+            for (int g16 = 0; g16 < kBK / 16; ++g16) {
                 bf16x8_t sa[MTM][3], sb[2][3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
                     for (int s_ = 0; s_ < MTM; ++s_) sa[s_][p] = *reinterpret_cast<const bf16x8_t*>(a16 + s_ * 32 * kSplitRow + p * 32 + g16 * 16);
                 if constexpr (KIND == 2) {
-                    // a lane whose tap is off the image reads the zero row (one select on the address per tap and fragment)
+                    // [column][kSplitRow] image: this lane's (shifted) column per fragment, read like the weights
                     const __bf16* c0 = Bs16 + (ok0 ? jb[0] + delta : jz) * kSplitRow + 8 * (lane >> 5) + g16 * 16;
                     const __bf16* c1 = Bs16 + (ok1 ? jb[1] + delta : jz) * kSplitRow + 8 * (lane >> 5) + g16 * 16;
 #pragma unroll
@@ -721,10 +708,9 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
                     for (int sn = 0; sn < 2; ++sn)
 #pragma unroll
                         for (int p = 0; p < 3; ++p) {
-                            const __bf16* base = Bs16 + (p * fBK + krow) * fSplitPixRow + wn * 64 + sn * 32 + 16 * u + 4 * pp;
+                            const __bf16* base = Bs16 + (p * kBK + krow) * fSplitPixRow + wn * 64 + sn * 32 + 16 * u + 4 * pp;
                             const s16x4_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(base));
                             const s16x4_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(base + 4 * fSplitPixRow));
-                            typedef short s16x8_t __attribute__((ext_vector_type(8)));
                             const s16x8_t both = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
                             sb[sn][p] = __builtin_bit_cast(bf16x8_t, both);
                         }
@@ -735,45 +721,20 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
                     acc[sm][1] = split3_mfma(sa[sm], sb[1], acc[sm][1]);
                 }
             }
-            return;
-        }
-        if constexpr (KIND == 2) {
-            // [column][k] image: a lane's four k of an MFMA group are ONE 16-byte read; a lane whose tap is off the image
-            // reads the zero row (one select on the address per tap and fragment instead of one per value)
-            const float* c0 = Bs + (ok0 ? jb[0] + delta : jz) * fFlatPix + 4 * (lane >> 5);
-            const float* c1 = Bs + (ok1 ? jb[1] + delta : jz) * fFlatPix + 4 * (lane >> 5);
-#pragma unroll
-            for (int kk = 0; kk < fBK / 8; ++kk) {
-                f32x4 fa[MTM];
-#pragma unroll
-                for (int s = 0; s < MTM; ++s) fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * fLdsA + kk * 8);
-                const f32x4 f0 = *reinterpret_cast<const f32x4*>(c0 + kk * 8), f1 = *reinterpret_cast<const f32x4*>(c1 + kk * 8);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int sm = 0; sm < MTM; ++sm) {
-                        acc[sm][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], f0[e], acc[sm][0], 0, 0, 0);
-                        acc[sm][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], f1[e], acc[sm][1], 0, 0, 0);
-                    }
-            }
-            return;
-        }
-        // the 1 x 1 forms (one tap, no shift)
-        const float* b0 = bb + (ok0 ? jb[0] : jz);
-        const float* b1 = bb + (ok1 ? jb[1] : jz);
-#pragma unroll
-        for (int kk = 0; kk < fBK / 8; ++kk) {
-            f32x4 fa[MTM];
-#pragma unroll
-            for (int s = 0; s < MTM; ++s) fa[s] = *reinterpret_cast<const f32x4*>(a + s * 32 * fLdsA + kk * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float f0 = b0[(kk * 8 + e) * Lr], f1 = b1[(kk * 8 + e) * Lr];
-#pragma unroll
-                for (int sm = 0; sm < MTM; ++sm) {
-                    acc[sm][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], f0, acc[sm][0], 0, 0, 0);
-                    acc[sm][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sm][e], f1, acc[sm][1], 0, 0, 0);
-                }
+        } else {
+            const float* a = As + abuf * TM * kLds + (wm * (TM / 2) + (lane & 31)) * kLds + 4 * (lane >> 5);
+            if constexpr (KIND == 2) {
+                // [column][k] image: a lane's four k of an MFMA group are ONE 16-byte read of its (shifted) column
+                const float* c[2] = {Bs + (ok0 ? jb[0] + delta : jz) * fFlatPix + 4 * (lane >> 5),
+                                     Bs + (ok1 ? jb[1] + delta : jz) * fFlatPix + 4 * (lane >> 5)};
+                nt_mma_fp32_from<TM, fTN>(a, [&](int sn, int kk) { return *reinterpret_cast<const f32x4*>(c[sn] + kk * 8); }, acc);
+            } else {
+                // 1 x 1 (one tap, no shift), [k][pixel] image: four 4-byte reads at stride Lr; half-wave h takes k = 8 kk + e + 4 h
+                const float* bb = Bs + bbuf * kBK * Lr + 4 * (lane >> 5) * Lr;
+                const float* c[2] = {bb + (ok0 ? jb[0] : jz), bb + (ok1 ? jb[1] : jz)};
+                nt_mma_fp32_from<TM, fTN>(a, [&](int sn, int kk) {
+                    return f32x4{c[sn][(kk * 8 + 0) * Lr], c[sn][(kk * 8 + 1) * Lr], c[sn][(kk * 8 + 2) * Lr], c[sn][(kk * 8 + 3) * Lr]};
+                }, acc);
             }
         }
     };
@@ -785,15 +746,13 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
         }                                // 1 x 1: pixels past the tensor's end are stored as zeros (no zero column)
     } else if constexpr (KIND == 2) {
         if (tid < fFlatPix / 4) *reinterpret_cast<f32x4*>(Bs + jz * fFlatPix + 4 * tid) = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else if (tid < fBK * NBUF) Bs[tid * Lr + jz] = 0.f;
+    } else if (tid < kBK * NBUF) Bs[tid * Lr + jz] = 0.f;
     load_a(0, 0, ra0);
     load_b(0, rb0);
     store_a(0, ra0);
     store_b(0, rb0);
     __syncthreads();
-    constexpr int ROWS = TM / 8;
-    int m1[ROWS], m2[ROWS];
-    float bias_v[ROWS];
+    FwdRowOps<TM, PLAIN> ops;
     // Software pipeline, two chunks deep for the global loads: while chunk c computes, the operands of chunk c + 1 are in
     // flight or in registers (requested one iteration earlier) and those of chunk c + 2 are requested.  k x k forms load
     // the input image of the next channel block two taps before its first use.
@@ -858,10 +817,10 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
         step(c, r, ra1, ra0, rb1, rb0);
         r = ra_;
     }
-    fwd_load_maps<TM, PLAIN>(L, i0, m1, m2, bias_v);        // epilogue operands, requested under the last chunk's MFMAs
+    fwd_load_maps<TM, PLAIN>(L, i0, ops);                   // epilogue operands, requested under the last chunk's MFMAs
     compute((nchunks - 1) & 1, bsel, r);
     __syncthreads();
-    fwd_epilogue<TM, PLAIN>(L, it, acc, m1, m2, bias_v, smem, partials);
+    fwd_epilogue<TM, PLAIN>(L, it, acc, ops, smem, partials);
 }
 
 // One kernel per tile form (register allocation and LDS are then per form, not the maximum over all of them); the host
@@ -901,7 +860,7 @@ constexpr bool fwd_forms_match_variants() {
 }
 static_assert(fwd_forms_match_variants(), "kFwdForms is indexed by the form id");
 template <int FORM, int SPLIT = 0>
-__global__ __launch_bounds__(fThreads, kFwdForms[FORM].occupancy[SPLIT]) void fwd_batch_kernel(const FwdLayerDev* __restrict__ layers,
+__global__ __launch_bounds__(kThreads, kFwdForms[FORM].occupancy[SPLIT]) void fwd_batch_kernel(const FwdLayerDev* __restrict__ layers,
                                                              const FwdItemDev* __restrict__ items,
                                                              float* __restrict__ partials) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -915,7 +874,7 @@ __global__ __launch_bounds__(fThreads, kFwdForms[FORM].occupancy[SPLIT]) void fw
 // A plain convolution (pleas_conv2d_fwd): ONE layer, described in the kernel arguments; the work item is the block index
 // (output-channel tile fastest, as in the grouped plan), no tables, no target, no loss.
 template <int FORM, int SPLIT = 0, int BN = 0>
-__global__ __launch_bounds__(fThreads, kFwdForms[FORM].occupancy[SPLIT]) void conv2d_fwd_kernel(const FwdLayerDev L, const int tms) {
+__global__ __launch_bounds__(kThreads, kFwdForms[FORM].occupancy[SPLIT]) void conv2d_fwd_kernel(const FwdLayerDev L, const int tms) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const FwdItemDev it{0, (int)(blockIdx.x % (unsigned)tms), (int)(blockIdx.x / (unsigned)tms), 0};
     constexpr FwdForm F = kFwdForms[FORM];
@@ -1041,10 +1000,10 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
     const int TM = l.Cout > 64 ? 128 : 64;
     d.variant = (TM == 64 ? 1 : 0) | (Kd % 4 == 0 ? 0 : 2);
     if (l.flags & PLEAS_FWD_KPOS_MAJOR) {
-        if (l.Cin % fBK != 0) return bad_arg("conv_fwd: kernel-position-major weights need Cin % 32 == 0");
+        if (l.Cin % kBK != 0) return bad_arg("conv_fwd: kernel-position-major weights need Cin % 32 == 0");
         d.variant |= 4;
     }
-    lds_bytes = (size_t)(2 * TM * fLdsA + 2 * fTN * fLdsB) * sizeof(float);  // >= TM*132 floats (epilogue)
+    lds_bytes = (size_t)(2 * TM * kLds + 2 * fTN * kLds) * sizeof(float);  // >= TM*132 floats (epilogue)
     {
         // flat-shift form: stride 1, square odd kernel with "same" padding, whole 32-channel blocks, and (for k > 1)
         // kernel-position-major weights; its LDS must not exceed the general form's (two workgroups per CU)
@@ -1053,16 +1012,16 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
         const int halo = l.pad * (l.Win + 1);
         const int kind = R > 1 ? 2 : (HWo % 4 == 0 ? 0 : 1);
         const int Lr = kind == 2 ? fFlatColsK : fFlatRow1;      // k x k: columns of the [column][36] image, zero row included
-        const size_t flat_lds = std::max((size_t)(2 * TM * fLdsA + (kind == 2 ? fFlatColsK * fFlatPix : 2 * fBK * Lr)) * sizeof(float),
+        const size_t flat_lds = std::max((size_t)(2 * TM * kLds + (kind == 2 ? fFlatColsK * fFlatPix : 2 * kBK * Lr)) * sizeof(float),
                                          (size_t)TM * 132 * sizeof(float));
-        if (same && l.Cin % fBK == 0 && R <= 32 && (R == 1 || (l.flags & PLEAS_FWD_KPOS_MAJOR)) &&
+        if (same && l.Cin % kBK == 0 && R <= 32 && (R == 1 || (l.flags & PLEAS_FWD_KPOS_MAJOR)) &&
             fTN + 2 * halo < Lr && flat_lds <= lds_bytes && (int64_t)l.N * l.Cin * HWo < (1ll << 32)) {
             d.variant |= 8 | (kind << 4);
             lds_bytes = flat_lds;
             if (arith_mode() == 1 && kind != 1) {
                 // split-bf16 images (fwd_flat_tile<.., SPLIT = 1>): weights [TM][kSplitRow] + input k x k [columns][kSplitRow] /
                 // 1 x 1 [3][32][fSplitPixRow] bf16, ONE image each; the epilogue stages [TM][132] floats in the same memory
-                const size_t img = (size_t)(TM * kSplitRow + (kind == 2 ? fFlatColsK * kSplitRow : 3 * fBK * fSplitPixRow)) * sizeof(__bf16);
+                const size_t img = (size_t)(TM * kSplitRow + (kind == 2 ? fFlatColsK * kSplitRow : 3 * kBK * fSplitPixRow)) * sizeof(__bf16);
                 lds_bytes = std::max(img, (size_t)TM * 132 * sizeof(float));
             }
         }
@@ -1101,7 +1060,7 @@ static int build_fwd_plan(FwdPlan& P, const pleas_fwd_layer* ly, int n) {
             for (int tm = 0; tm < tms; ++tm) {
                 XcdWork<FwdItemDev> w;
                 w.it = FwdItemDev{i, tm, tp, slot++};
-                w.w = (double)ceil_div(Kd, fBK) * TM;
+                w.w = (double)ceil_div(Kd, kBK) * TM;
                 // all items of a layer re-read its weights (and, across tm, its input): keep them on one XCD; layers
                 // with many pixel tiles are cut into runs of 32 tiles so that the 8 queues still balance
                 w.key = (int64_t)i * 65536 + tp / 32;
@@ -1127,7 +1086,7 @@ static int build_fwd_plan(FwdPlan& P, const pleas_fwd_layer* ly, int n) {
     for (size_t k = 0; k < P.items.size(); ++k)
         if (P.items[k].layer >= 0) {
             const FwdLayerDev& d = P.layers[P.items[k].layer];
-            P.item_work[k] = (float)(ceil_div(d.Kd, fBK) * kFwdForms[fwd_form_of(d.variant)].tm);
+            P.item_work[k] = (float)(ceil_div(d.Kd, kBK) * kFwdForms[fwd_form_of(d.variant)].tm);
         }
     // launch order: the form with the most work first (its tail is then covered by nothing, the small ones' tails are short).
     // The forms' static weights deal the FIRST launches of a plan only; launch kFwdCalibAt measures every form on its lane and
@@ -1227,7 +1186,7 @@ static int conv2d_launch(const float* x, const float* w, const float* bias, floa
     const double out_floats = (double)Cout * d.Ptot;
     ProfScope prof(kProfConv2d, 2.0 * Cout * (double)d.Kd * (double)d.Ptot,
                    ((double)Cin * N * Hin * Win + out_floats * (bn ? (res ? 3.0 : 2.0) : 1.0)) * sizeof(float), st);
-    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? 1 : 0][arith_mode() == 1 ? 1 : 0], grid, dim3(fThreads), lds, st, d, tms);
+    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? 1 : 0][arith_mode() == 1 ? 1 : 0], grid, dim3(kThreads), lds, st, d, tms);
     PLEAS_LAUNCH_CHECK("conv2d_fwd_kernel");
     return PLEAS_OK;
 }
@@ -1285,7 +1244,7 @@ static int fwd_launch_units(FwdPlan& P, const FwdLayerDev* dl, const FwdItemDev*
         if (lane > 0 && !lane_used[lane]) PLEAS_HIP_CHECK(hipStreamWaitEvent(st, side.forked, 0));
         lane_used[lane] = true;
         if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t0[o], st));
-        hipLaunchKernelGGL(kFwdKernels[un.form].batch[P.split ? 1 : 0], dim3((unsigned)un.count), dim3(fThreads), P.form_lds[un.form], st,
+        hipLaunchKernelGGL(kFwdKernels[un.form].batch[P.split ? 1 : 0], dim3((unsigned)un.count), dim3(kThreads), P.form_lds[un.form], st,
                            dl, items + un.begin, parts);
         if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t1[o], st));
     }
