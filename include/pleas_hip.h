@@ -375,7 +375,7 @@ int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, void* ws, s
 /* Host only (no GPU): what the plan builder of pleas_wgrad_batch decides for `layers` under the current pleas_arith, six ints
  * per layer: [0] the tile form `variant` (bit 0: 64-row tiles, bit 1: 64-column tiles, bit 2: scalar loads of the residual,
  * bit 3: shifted one-pixel loader of the input, bit 4: shifted through aligned 16-byte loads, bit 5: "virtual channels" --
- * rows are (channel, tap) pairs, layers with fewer than 16 input channels --, bit 6: split-bf16 kernel), [1] S, the slabs of
+ * rows are (channel, tap) pairs, layers with fewer than 16 input channels --, bit 6: split-bf16 kernel, either product count), [1] S, the slabs of
  * the pixel axis (> 1: slabs + reduce), [2] / [3] output-channel / input-channel tiles, [4] work items, [5] 1 when the
  * epilogue stages the tile through LDS and writes 16-byte rows (the pointers may be NULL: a 16-byte aligned gradient and
  * workspace are assumed then).  Returns 0 or a negative error code. */
@@ -450,13 +450,21 @@ void pleas_gram_batch_tune(int item_chunks, int xcd_order);
 /* Arithmetic of the contraction kernels (matching contraction, grouped forward, weight gradient, plain convolution).
  *   PLEAS_ARITH_FP32       (default) exact fp32 MFMA, v_mfma_f32_32x32x2_f32: bitwise an fmaf chain;
  *   PLEAS_ARITH_SPLIT_BF16 every fp32 operand as the exact sum of three bf16 values, six v_mfma_f32_32x32x16_bf16 products per
- *                          k step with fp32 accumulation (the three dropped terms are below half an fp32 ulp of the product):
- *                          fp32 accuracy at 2.67x less matrix-pipe time.  Tile forms without a split variant (scalar-load
- *                          forms: 7 x 7 images, strided layers, the stem) keep the exact arithmetic inside the same launch.
- * Process-wide; plans are keyed by it.  PLEAS_ARITH=split_bf16 in the environment sets the initial value.  The headline
- * numbers and every default-path test run with PLEAS_ARITH_FP32; bench.py reports the other as `alt_arith`. */
+ *                          k step with fp32 accumulation.  The three dropped terms (x2 y3 + x3 y2 + x3 y3) sum to as much as
+ *                          about 2^-25 .. 2^-24 of the product, half to one fp32 ulp: marginally narrower than an fmaf chain,
+ *                          at 2.67x less matrix-pipe time.  Tile forms without a split variant (scalar-load forms: 7 x 7
+ *                          images, strided layers, the stem) keep the exact arithmetic inside the same launch.
+ *   PLEAS_ARITH_SPLIT_BF16_EXACT  the same split with all nine products: every bf16 x bf16 product is exact in fp32 and the
+ *                          three planes sum exactly to the operand, so every fp32 product enters the sum exactly; the only
+ *                          rounding is the fp32 accumulation (one per MFMA, 16 k deep).  1.78x less matrix-pipe time than
+ *                          fp32 MFMA.  Same forms, plans, LDS images and exact-only forms as PLEAS_ARITH_SPLIT_BF16; kernels
+ *                          of its own.
+ * Any other value selects PLEAS_ARITH_FP32.  Process-wide; plans are keyed by it.  PLEAS_ARITH=split_bf16 (or 1) /
+ * PLEAS_ARITH=split_bf16_exact (or 2) in the environment sets the initial value.  The headline numbers and every default-path
+ * test run with PLEAS_ARITH_FP32; bench.py reports PLEAS_ARITH_SPLIT_BF16 as `alt_arith`. */
 #define PLEAS_ARITH_FP32 0
 #define PLEAS_ARITH_SPLIT_BF16 1
+#define PLEAS_ARITH_SPLIT_BF16_EXACT 2
 void pleas_arith(int mode);
 int pleas_arith_get(void);
 

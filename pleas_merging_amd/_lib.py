@@ -13,6 +13,7 @@ _LIB: Optional[ctypes.CDLL] = None
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libpleas_hip.so")
 
 EPI_INNER, EPI_NEG_CDIST = 0, 1
+ARITH_FP32, ARITH_SPLIT_BF16, ARITH_SPLIT_BF16_EXACT = 0, 1, 2      # PLEAS_ARITH_*
 LSAP_MAX_N = 4096
 
 # name -> (restype, argtypes); one row per symbol declared in include/pleas_hip.h

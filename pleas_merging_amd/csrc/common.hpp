@@ -51,13 +51,16 @@ typedef __attribute__((address_space(1))) const int gcint;
 #define PLEAS_GLOBAL_W(p) ((::pleas::gfloat*)(p))
 #define PLEAS_GLOBAL_I(p) ((::pleas::gcint*)(p))
 
-// ---- alternative arithmetic of the contraction kernels (pleas_arith): an fp32 value as the EXACT sum of three bf16 values,
+// ---- alternative arithmetics of the contraction kernels (pleas_arith): an fp32 value as the EXACT sum of three bf16 values,
 // v = h1 + h2 + h3 (8 + 8 + 8 significant bits, each the round-to-nearest bf16 of what the previous ones left; bf16 has
-// fp32's exponent range), so that an fp32 product becomes six bf16-MFMA products with fp32 accumulation:
-//   x * y = x1 y1 + (x1 y2 + x2 y1) + (x2 y2 + x1 y3 + x3 y1)  + terms <= 2^-26 |x y| (dropped: below half an fp32 ulp)
-// Six v_mfma_f32_32x32x16_bf16 (32 cycles each, K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles each, K = 2): 2.67x
-// less matrix-pipe time at fp32 accuracy.  The split is done once per element when a K chunk goes from registers to LDS.
-// Not for inf / NaN operands (inf - inf in the residual).
+// fp32's exponent range), so that an fp32 product becomes bf16-MFMA products with fp32 accumulation.  Every bf16 x bf16
+// product has at most 16 significant bits: it is exact in fp32, the only rounding is the accumulation.
+//   six products (PLEAS_ARITH_SPLIT_BF16):  x * y = x1 y1 + (x1 y2 + x2 y1) + (x2 y2 + x1 y3 + x3 y1) + dropped terms
+//     dropped: x2 y3 + x3 y2 + x3 y3, up to about 2^-25 .. 2^-24 |x y|: half to one fp32 ulp of the product
+//   nine products (PLEAS_ARITH_SPLIT_BF16_EXACT): nothing dropped, every fp32 product is summed exactly as its nine parts
+// Six (nine) v_mfma_f32_32x32x16_bf16 (32 cycles each, K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles each, K = 2):
+// 2.67x (1.78x) less matrix-pipe time.  The split is done once per element when a K chunk goes from registers to LDS, the same
+// way for both: the two differ only in the MFMA list.  Not for inf / NaN operands (inf - inf in the residual).
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -90,9 +93,16 @@ __device__ __forceinline__ void split3_store4(__bf16* row, int col, float v0, fl
 #pragma unroll
     for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2_t*>(row + p * 32 + col) = u32x2_t{lo[p], hi[p]};
 }
-// the six products of one 16-deep k step, smallest terms first
+// the products of one 16-deep k step, smallest terms first: NPROD = 6 (x2 y3, x3 y2, x3 y3 dropped) or all 9
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
+template <int NPROD = 6>
 __device__ __forceinline__ f32x16_t split3_mfma(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x16_t c) {
+    static_assert(NPROD == 6 || NPROD == 9, "six or nine of the nine bf16 products");
+    if constexpr (NPROD == 9) {
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[2], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[2], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[1], c, 0, 0, 0);
+    }
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
@@ -101,7 +111,10 @@ __device__ __forceinline__ f32x16_t split3_mfma(const bf16x8_t (&a)[3], const bf
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
     return c;
 }
-// process-wide arithmetic switch (pleas_arith): 0 = exact fp32 MFMA (default), 1 = split bf16 where a kernel has the form
+// SPLIT (the kernels' template parameter = pleas_arith's mode: 0 exact, 1 six products, 2 nine) -> products per step
+constexpr int split_products(int split) { return split == 2 ? 9 : 6; }
+// process-wide arithmetic switch (pleas_arith): 0 = exact fp32 MFMA (default), 1 / 2 = split bf16 with six / nine products where
+// a kernel has the form
 int arith_mode();
 
 

@@ -58,8 +58,9 @@ struct WgradItemDev {
 // ONE 16-byte load at a 4-byte-aligned address (the hardware takes it; two aligned loads + a register shift move twice the
 // bytes through the 64 B/clk vector L1 and measured 5 % SLOWER than one pixel per load); nothing of Y is masked -- the
 // taps that fall off the image are voided by zeroing the RESIDUAL at those output pixels (a rectangle of (oh, ow)).
-// SPLIT = 1 (pleas_arith(PLEAS_ARITH_SPLIT_BF16); 16-byte-loadable operands only: YMODE 0 / 2): the chunk goes to LDS as three
-// bf16 planes per row (common.hpp), ONE image per operand, two barriers per chunk, six v_mfma_f32_32x32x16_bf16 per k step.
+// SPLIT = 1 / 2 (pleas_arith(PLEAS_ARITH_SPLIT_BF16 / _EXACT); 16-byte-loadable operands only: YMODE 0 / 2): the chunk goes to LDS
+// as three bf16 planes per row (common.hpp), ONE image per operand, two barriers per chunk, six / nine v_mfma_f32_32x32x16_bf16
+// per k step.
 template <int TM, int TN, int VECX, int YMODE, int SPLIT = 0>
 __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradItemDev& it, float* smem) {
     static_assert(!SPLIT || (VECX == 4 && (YMODE == 0 || YMODE == 2)), "the split image is written four k at a time");
@@ -279,7 +280,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
         }
     };
     nt_pipeline<SPLIT>(it.c_begin, it.c_end, load_chunk, store_chunk, [&](int buf) {
-        if constexpr (SPLIT) nt_mma_split<TM, TN>(As16, Bs16, acc);
+        if constexpr (SPLIT) nt_mma_split<TM, TN, split_products(SPLIT)>(As16, Bs16, acc);
         else nt_mma_fp32<TM, TN>(As, Bs, buf, acc);
     });
 
@@ -362,10 +363,10 @@ __device__ __forceinline__ void wgrad_tile(const WgradLayerDev& L, const WgradIt
 
 // the split-bf16 forms: 16-byte-loadable operands only (1x1 stride-1 layers and stride-1 "same" k x k layers on images with
 // HW % 4 == 0); the plan sends every other layer's items to the exact kernel
-template <int TM, int TN>
+template <int TM, int TN, int SPLIT>
 __device__ __forceinline__ void wgrad_dispatch_split(const WgradLayerDev& L, const WgradItemDev& it, float* smem) {
-    if (L.variant & 16) wgrad_tile<TM, TN, 4, 2, 1>(L, it, smem);
-    else wgrad_tile<TM, TN, 4, 0, 1>(L, it, smem);
+    if (L.variant & 16) wgrad_tile<TM, TN, 4, 2, SPLIT>(L, it, smem);
+    else wgrad_tile<TM, TN, 4, 0, SPLIT>(L, it, smem);
 }
 
 template <int TM, int TN>
@@ -395,6 +396,7 @@ __global__ __launch_bounds__(kThreads, 2) void wgrad_batch_kernel(const WgradLay
     }
 }
 
+template <int SPLIT>      // 1 / 2: six / nine products, a kernel each
 __global__ __launch_bounds__(kThreads, 3) void wgrad_batch_split_kernel(const WgradLayerDev* __restrict__ layers,
                                                                      const WgradItemDev* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -402,10 +404,10 @@ __global__ __launch_bounds__(kThreads, 3) void wgrad_batch_split_kernel(const Wg
     if (it.layer < 0) return;   // padding of the XCD-aware item order
     const WgradLayerDev L = layers[it.layer];
     switch (L.variant & 3) {  // block-uniform
-        case 0: wgrad_dispatch_split<128, 128>(L, it, smem); break;
-        case 1: wgrad_dispatch_split<64, 128>(L, it, smem); break;
-        case 2: wgrad_dispatch_split<128, 64>(L, it, smem); break;
-        default: wgrad_dispatch_split<64, 64>(L, it, smem); break;
+        case 0: wgrad_dispatch_split<128, 128, SPLIT>(L, it, smem); break;
+        case 1: wgrad_dispatch_split<64, 128, SPLIT>(L, it, smem); break;
+        case 2: wgrad_dispatch_split<128, 64, SPLIT>(L, it, smem); break;
+        default: wgrad_dispatch_split<64, 64, SPLIT>(L, it, smem); break;
     }
 }
 
@@ -538,6 +540,7 @@ struct WgradPlan {
     double flops = 0, bytes = 0;
     bool uploaded = false;
     int n_split = 0;         // items [0, n_split) run the split-bf16 kernel, the rest the exact one (pleas_arith)
+    int split = 0;           // pleas_arith's mode the plan was built under: which split kernel (1 / 2)
     size_t lds_split = 0;
     double flops_split = 0;
 };
@@ -556,7 +559,8 @@ static int build_wgrad_plan(WgradPlan& P, const pleas_wgrad_layer* ly, int n) {
     std::vector<size_t> slab_off(n, 0);
     size_t slabs = 0;
     std::vector<XcdWork<WgradItemDev>> work, work_split;
-    const bool split_on = arith_mode() == 1;
+    P.split = arith_mode();
+    const bool split_on = P.split != 0;
     P.n_split = 0;
     P.lds_split = 0;
     P.flops_split = 0;
@@ -772,7 +776,8 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
             PLEAS_LAUNCH_CHECK("wgrad_batch_kernel");
         }
         if (P.n_split > 0) {
-            hipLaunchKernelGGL(wgrad_batch_split_kernel, dim3((unsigned)P.n_split), dim3(kThreads), P.lds_split, stream, dl, its);
+            hipLaunchKernelGGL(P.split == 2 ? wgrad_batch_split_kernel<2> : wgrad_batch_split_kernel<1>, dim3((unsigned)P.n_split),
+                               dim3(kThreads), P.lds_split, stream, dl, its);
             PLEAS_LAUNCH_CHECK("wgrad_batch_split_kernel");
         }
         if (fork) {

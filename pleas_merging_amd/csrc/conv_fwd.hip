@@ -454,8 +454,8 @@ constexpr int fFlatColsK = 248;    // columns of that image: 128 + 2 * halo data
 // KIND 0: 1x1, 16-B loads along the pixel axis (HW % 4 == 0), two images (double buffer)
 // KIND 1: 1x1, scalar loads (HW % 4 != 0, e.g. 7 x 7), two images
 // KIND 2: k x k, scalar loads, ONE image per channel block shared by all taps
-// SPLIT = 1 (pleas_arith(PLEAS_ARITH_SPLIT_BF16); KIND 0 and 2): every chunk goes to LDS as three bf16 planes (common.hpp), ONE
-// image per operand (two barriers per chunk), six v_mfma_f32_32x32x16_bf16 per 16-deep k step.
+// SPLIT = 1 / 2 (pleas_arith(PLEAS_ARITH_SPLIT_BF16 / _EXACT); KIND 0 and 2): every chunk goes to LDS as three bf16 planes
+// (common.hpp), ONE image per operand (two barriers per chunk), six / nine v_mfma_f32_32x32x16_bf16 per 16-deep k step.
 //   weights:      [TM][kSplitRow] rows (3 planes x 32 k), fragments by ds_read_b128 -- the operand map of the MFMA
 //   k x k input:  [column][kSplitRow], a pixel's 32 channels contiguous per plane: the same 16-byte fragment reads
 //   1 x 1 input:  [plane][k][fSplitPixRow] (pixels contiguous, as they come from memory: 8-byte writes), fragments by
@@ -717,9 +717,12 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
                 }
 #pragma unroll
                 for (int sm = 0; sm < MTM; ++sm) {
-                    acc[sm][0] = split3_mfma(sa[sm], sb[0], acc[sm][0]);
-                    acc[sm][1] = split3_mfma(sa[sm], sb[1], acc[sm][1]);
+                    acc[sm][0] = split3_mfma<split_products(SPLIT)>(sa[sm], sb[0], acc[sm][0]);
+                    acc[sm][1] = split3_mfma<split_products(SPLIT)>(sa[sm], sb[1], acc[sm][1]);
                 }
+                // nine products: nothing moves across the end of a k group.  Left to itself the scheduler keeps three values more
+                // alive than the 256 registers of two workgroups per CU hold (the plain 128-row 1 x 1 kernel spilled 12 bytes).
+                if constexpr (SPLIT == 2) __builtin_amdgcn_sched_barrier(0);
             }
         } else {
             const float* a = As + abuf * TM * kLds + (wm * (TM / 2) + (lane & 31)) * kLds + 4 * (lane >> 5);
@@ -830,19 +833,19 @@ struct FwdForm {
     bool flat;        // fwd_flat_tile, else the general fwd_tile
     int tm;           // output channels of a tile
     int sub;          // general: floats per weight load (VECA); flat: KIND
-    bool split;       // a split-bf16 kernel exists (launched under pleas_arith(PLEAS_ARITH_SPLIT_BF16); the other forms run
-                      // their exact kernel in the same launch group)
-    int occupancy[2]; // workgroups per CU the exact / the split kernel is compiled for
+    bool split;       // split-bf16 kernels exist (launched under pleas_arith(PLEAS_ARITH_SPLIT_BF16 / _EXACT); the other forms
+                      // run their exact kernel in the same launch group)
+    int occupancy[3]; // workgroups per CU the exact / the six-product / the nine-product kernel is compiled for
     double weight;    // expected duration per unit of MFMA work (measured on the ResNet-101 list, each form alone): the general
                       // tile (stride-2 layers: few, long items; stem: scalar weight loads) runs at ~0.4x the flat forms' rate,
                       // the scalar-pixel 1 x 1 form (7 x 7 images) at ~0.5x
 };
 constexpr int fForms = 10;
 constexpr FwdForm kFwdForms[fForms] = {
-    {false, 128, 4, false, {2, 2}, 2.5}, {false, 64, 4, false, {2, 2}, 2.5},
-    {false, 128, 1, false, {2, 2}, 2.5}, {false, 64, 1, false, {2, 2}, 2.5},
-    {true, 128, 0, true, {2, 2}, 1.0},   {true, 128, 1, false, {2, 2}, 2.0}, {true, 128, 2, true, {2, 2}, 1.0},
-    {true, 64, 0, true, {2, 3}, 1.0},    {true, 64, 1, false, {2, 2}, 2.0},  {true, 64, 2, true, {2, 3}, 1.0},
+    {false, 128, 4, false, {2, 2, 2}, 2.5}, {false, 64, 4, false, {2, 2, 2}, 2.5},
+    {false, 128, 1, false, {2, 2, 2}, 2.5}, {false, 64, 1, false, {2, 2, 2}, 2.5},
+    {true, 128, 0, true, {2, 2, 2}, 1.0},   {true, 128, 1, false, {2, 2, 2}, 2.0}, {true, 128, 2, true, {2, 2, 2}, 1.0},
+    {true, 64, 0, true, {2, 3, 3}, 1.0},    {true, 64, 1, false, {2, 2, 2}, 2.0},  {true, 64, 2, true, {2, 3, 3}, 1.0},
 };
 // the id of FwdLayerDev::variant's form
 constexpr int fwd_form_of(int variant) {
@@ -882,16 +885,17 @@ __global__ __launch_bounds__(kThreads, kFwdForms[FORM].occupancy[SPLIT]) void co
     if constexpr (F.flat) fwd_flat_tile<F.tm, F.sub, SPLIT, PLAIN>(L, it, smem, nullptr);
     else fwd_tile<F.tm, F.sub, PLAIN>(L, it, smem, nullptr);
 }
-// The kernels of a form, [split arithmetic]: a form without a split kernel keeps its exact one there.
+// The kernels of a form, [arithmetic = pleas_arith's mode]: a form without split kernels keeps its exact one there.
 struct FwdFormKernels {
-    void (*batch[2])(const FwdLayerDev*, const FwdItemDev*, float*);
-    void (*conv2d[2][2])(const FwdLayerDev, const int);      // [BN][split arithmetic]
+    void (*batch[3])(const FwdLayerDev*, const FwdItemDev*, float*);
+    void (*conv2d[2][3])(const FwdLayerDev, const int);      // [BN][arithmetic]
 };
 template <int FORM>
 static constexpr FwdFormKernels fwd_form_kernels() {
-    constexpr int S = kFwdForms[FORM].split ? 1 : 0;
-    return {{fwd_batch_kernel<FORM, 0>, fwd_batch_kernel<FORM, S>},
-            {{conv2d_fwd_kernel<FORM, 0, 0>, conv2d_fwd_kernel<FORM, S, 0>}, {conv2d_fwd_kernel<FORM, 0, 1>, conv2d_fwd_kernel<FORM, S, 1>}}};
+    constexpr int S = kFwdForms[FORM].split ? 1 : 0, S9 = kFwdForms[FORM].split ? 2 : 0;
+    return {{fwd_batch_kernel<FORM, 0>, fwd_batch_kernel<FORM, S>, fwd_batch_kernel<FORM, S9>},
+            {{conv2d_fwd_kernel<FORM, 0, 0>, conv2d_fwd_kernel<FORM, S, 0>, conv2d_fwd_kernel<FORM, S9, 0>},
+             {conv2d_fwd_kernel<FORM, 0, 1>, conv2d_fwd_kernel<FORM, S, 1>, conv2d_fwd_kernel<FORM, S9, 1>}}};
 }
 static const FwdFormKernels kFwdKernels[fForms] = {fwd_form_kernels<0>(), fwd_form_kernels<1>(), fwd_form_kernels<2>(), fwd_form_kernels<3>(),
                                                    fwd_form_kernels<4>(), fwd_form_kernels<5>(), fwd_form_kernels<6>(), fwd_form_kernels<7>(),
@@ -956,7 +960,7 @@ struct FwdPlan {
     double flops = 0, bytes = 0;
     int n_parts = 0;
     bool uploaded = false;
-    bool split = false;                // built under pleas_arith(PLEAS_ARITH_SPLIT_BF16): the flat forms launch their split kernels
+    int split = 0;                     // pleas_arith's mode the plan was built under: 1 / 2, the flat forms launch those split kernels
     // lanes from MEASURED durations: launch kFwdCalibAt of a plan brackets every unit's kernel with events on its lane; a
     // later launch that finds them complete deals the forms again, longest measured duration first
     int launches = 0, calib = 0;       // calib: 0 not measured yet, 1 events recorded, 2 lanes dealt from measurements
@@ -1018,8 +1022,8 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
             fTN + 2 * halo < Lr && flat_lds <= lds_bytes && (int64_t)l.N * l.Cin * HWo < (1ll << 32)) {
             d.variant |= 8 | (kind << 4);
             lds_bytes = flat_lds;
-            if (arith_mode() == 1 && kind != 1) {
-                // split-bf16 images (fwd_flat_tile<.., SPLIT = 1>): weights [TM][kSplitRow] + input k x k [columns][kSplitRow] /
+            if (arith_mode() != 0 && kind != 1) {
+                // split-bf16 images (fwd_flat_tile<.., SPLIT = 1 / 2>): weights [TM][kSplitRow] + input k x k [columns][kSplitRow] /
                 // 1 x 1 [3][32][fSplitPixRow] bf16, ONE image each; the epilogue stages [TM][132] floats in the same memory
                 const size_t img = (size_t)(TM * kSplitRow + (kind == 2 ? fFlatColsK * kSplitRow : 3 * kBK * fSplitPixRow)) * sizeof(__bf16);
                 lds_bytes = std::max(img, (size_t)TM * 132 * sizeof(float));
@@ -1033,7 +1037,7 @@ static int fwd_describe(const pleas_fwd_layer& l, FwdLayerDev& d, size_t& lds_by
 static std::mutex g_fplan_mu;
 
 static int build_fwd_plan(FwdPlan& P, const pleas_fwd_layer* ly, int n) {
-    P.split = arith_mode() == 1;
+    P.split = arith_mode();
     P.layers.assign(n, FwdLayerDev());
     P.items.clear();
     for (int f = 0; f < fForms; ++f) P.form_begin[f] = P.form_count[f] = 0;
@@ -1186,7 +1190,7 @@ static int conv2d_launch(const float* x, const float* w, const float* bias, floa
     const double out_floats = (double)Cout * d.Ptot;
     ProfScope prof(kProfConv2d, 2.0 * Cout * (double)d.Kd * (double)d.Ptot,
                    ((double)Cin * N * Hin * Win + out_floats * (bn ? (res ? 3.0 : 2.0) : 1.0)) * sizeof(float), st);
-    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? 1 : 0][arith_mode() == 1 ? 1 : 0], grid, dim3(kThreads), lds, st, d, tms);
+    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? 1 : 0][arith_mode()], grid, dim3(kThreads), lds, st, d, tms);
     PLEAS_LAUNCH_CHECK("conv2d_fwd_kernel");
     return PLEAS_OK;
 }
@@ -1244,7 +1248,7 @@ static int fwd_launch_units(FwdPlan& P, const FwdLayerDev* dl, const FwdItemDev*
         if (lane > 0 && !lane_used[lane]) PLEAS_HIP_CHECK(hipStreamWaitEvent(st, side.forked, 0));
         lane_used[lane] = true;
         if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t0[o], st));
-        hipLaunchKernelGGL(kFwdKernels[un.form].batch[P.split ? 1 : 0], dim3((unsigned)un.count), dim3(kThreads), P.form_lds[un.form], st,
+        hipLaunchKernelGGL(kFwdKernels[un.form].batch[P.split], dim3((unsigned)un.count), dim3(kThreads), P.form_lds[un.form], st,
                            dl, items + un.begin, parts);
         if (measure) PLEAS_HIP_CHECK(hipEventRecord(P.t1[o], st));
     }
@@ -1269,8 +1273,9 @@ extern "C" int pleas_fwd_batch(const pleas_fwd_layer* layers, int n_layers, floa
     hipStream_t stream = (hipStream_t)stream_;
     std::lock_guard<std::mutex> lk(g_fplan_mu);
     std::vector<int64_t> key;
-    key.push_back(n_layers * 2 + arith_mode());      // plans (LDS sizes, kernels) differ between the arithmetics
+    key.push_back(n_layers);
     key.push_back((int64_t)(uintptr_t)ws);
+    key.push_back(arith_mode());      // plans (LDS sizes, kernels) differ between the arithmetics
     for (int i = 0; i < n_layers; ++i) {
         const pleas_fwd_layer& l = layers[i];
         for (int v : {l.N, l.Cout, l.Cin, l.Hin, l.Win, l.KH, l.KW, l.stride, l.pad, l.Csrc, l.n_merged, l.flags})

@@ -51,8 +51,8 @@ struct Stage {
     float v[PASSES][VEC];
 };
 
-// SPLIT = 1: the split-bf16 arithmetic of pleas_arith (common.hpp); its LDS image is single-buffered (nt_tile.hpp), and two
-// workgroups per CU alternate between converting and multiplying.
+// SPLIT = 1 / 2: the split-bf16 arithmetics of pleas_arith (common.hpp: six / nine products); their LDS image is single-buffered
+// (nt_tile.hpp), and two workgroups per CU alternate between converting and multiplying.
 
 // One workgroup's share: output tile (tm, tn) over K chunks [c_begin, c_end) -> slab `split`.
 template <int TILE, int VEC, int SPLIT = 0, int PAD = 0>
@@ -227,7 +227,7 @@ __device__ __forceinline__ void gram_tile(const GramGeom& g, float* smem, const 
         }
     };
     nt_pipeline<SPLIT>(c_begin, c_end, load_chunk, store_chunk, [&](int buf) {
-        if constexpr (SPLIT) nt_mma_split<TILE, TILE>(As16, Bs16, acc);
+        if constexpr (SPLIT) nt_mma_split<TILE, TILE, split_products(SPLIT)>(As16, Bs16, acc);
         else nt_mma_fp32<TILE, TILE>(As, Bs, buf, acc);
     });
 
@@ -277,8 +277,8 @@ __device__ __forceinline__ void gram_tile(const GramGeom& g, float* smem, const 
     }
 }
 
-// Single-node launch: grid = tiles x tiles x S.  The exact and the split arithmetic are kernels of their own (here and in the
-// grouped launch), so that the exact kernel's register allocation does not depend on the split one.
+// Single-node launch: grid = tiles x tiles x S.  Every arithmetic has kernels of its own (here and in the grouped launch), so
+// that no kernel's register allocation depends on another's.
 template <int TILE, int VEC, int SPLIT>
 __device__ __forceinline__ void gram_partial_body(const GramGeom& g, float* smem) {
     int bid = blockIdx.x;
@@ -296,10 +296,11 @@ __global__ __launch_bounds__(kThreads) void gram_partial_kernel(const GramGeom g
     gram_partial_body<TILE, VEC, 0>(g, smem);
 }
 
-template <int TILE, int VEC>
-__global__ __launch_bounds__(kThreads) void gram_partial_split_kernel(const GramGeom g) {
+// (the nine-product 64-row kernel is held to the five waves per SIMD the six-product one reaches by itself; 1 = no constraint)
+template <int TILE, int VEC, int SPLIT = 1>
+__global__ __launch_bounds__(kThreads, SPLIT == 2 && TILE == 64 ? 5 : 1) void gram_partial_split_kernel(const GramGeom g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    gram_partial_body<TILE, VEC, 1>(g, smem);
+    gram_partial_body<TILE, VEC, SPLIT>(g, smem);
 }
 
 // ---- grouped launch: every tracked node of a batch in ONE grid --------------------------------
@@ -369,10 +370,11 @@ __global__ __launch_bounds__(kThreads, 2) void gram_batch_kernel(const GramNodeD
     gram_batch_body<0>(nodes, items, smem);
 }
 
+template <int SPLIT>
 __global__ __launch_bounds__(kThreads, 2) void gram_batch_split_kernel(const GramNodeDev* __restrict__ nodes,
                                                                     const GramItemDev* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    gram_batch_body<1>(nodes, items, smem);
+    gram_batch_body<SPLIT>(nodes, items, smem);
 }
 
 // Writes the per-batch operand pointers into the device node table (kernel arguments carry them,
@@ -499,8 +501,8 @@ static GramPlan make_plan(int B, int C, int64_t HW, bool aligned) {
 
 using namespace pleas;
 
-// the matching contraction under pleas_arith(PLEAS_ARITH_SPLIT_BF16): gram_tile<TILE, 4, SPLIT = 1> on 16-byte-loadable nodes
-static bool split_bf16() { return arith_mode() == 1; }
+// The matching contraction under pleas_arith(PLEAS_ARITH_SPLIT_BF16 / _EXACT): gram_tile<TILE, 4, SPLIT = arith_mode()> on
+// 16-byte-loadable nodes.
 
 extern "C" size_t pleas_gram_ws_bytes(int B, int C, int64_t HW) {
     if (B <= 0 || C <= 0 || HW <= 0) return 0;
@@ -539,9 +541,13 @@ extern "C" int pleas_gram_accum(const float* x, const float* y, int B, int C, in
     const double kk = (double)B * (double)HW;
     {
     ProfScope prof(kProfGramPartial, 2.0 * C * (double)C * kk, 2.0 * C * kk * sizeof(float), stream);
-    if (p.vec == 4 && split_bf16()) {
+    if (const int split = arith_mode(); p.vec == 4 && split) {
         const size_t lds16 = (size_t)2 * p.tile * kSplitRow * sizeof(__bf16);      // 52 KB at tile 128
-        if (p.tile == 128)
+        if (p.tile == 128 && split == 2)
+            hipLaunchKernelGGL((gram_partial_split_kernel<128, 4, 2>), grid, dim3(kThreads), lds16, stream, g);
+        else if (split == 2)
+            hipLaunchKernelGGL((gram_partial_split_kernel<64, 4, 2>), grid, dim3(kThreads), lds16, stream, g);
+        else if (p.tile == 128)
             hipLaunchKernelGGL((gram_partial_split_kernel<128, 4>), grid, dim3(kThreads), lds16, stream, g);
         else
             hipLaunchKernelGGL((gram_partial_split_kernel<64, 4>), grid, dim3(kThreads), lds16, stream, g);
@@ -791,8 +797,11 @@ extern "C" int pleas_gram_batch(const pleas_gram_node* nodes, int n_nodes, float
     }
     {
         ProfScope prof(kProfGramPartial, P.flops, P.bytes, stream);
-        if (split_bf16())
-            hipLaunchKernelGGL(gram_batch_split_kernel, dim3((unsigned)P.items.size()), dim3(kThreads), P.lds, stream, dnodes,
+        if (const int split = arith_mode(); split == 2)
+            hipLaunchKernelGGL(gram_batch_split_kernel<2>, dim3((unsigned)P.items.size()), dim3(kThreads), P.lds, stream, dnodes,
+                               reinterpret_cast<const GramItemDev*>(base + P.off_items));
+        else if (split == 1)
+            hipLaunchKernelGGL(gram_batch_split_kernel<1>, dim3((unsigned)P.items.size()), dim3(kThreads), P.lds, stream, dnodes,
                                reinterpret_cast<const GramItemDev*>(base + P.off_items));
         else
             hipLaunchKernelGGL(gram_batch_kernel, dim3((unsigned)P.items.size()), dim3(kThreads), P.lds, stream, dnodes,

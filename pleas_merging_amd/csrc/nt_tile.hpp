@@ -4,7 +4,7 @@
 // loaders (what differs between them) stay with them.
 //   exact fp32:  LDS [2][rows][kLds] floats per operand (double-buffered, one barrier per chunk), v_mfma_f32_32x32x2_f32
 //   split bf16:  LDS [rows][kSplitRow] bf16 per operand (common.hpp; ONE image, two barriers per chunk: the next chunk
-//                waits in registers), six v_mfma_f32_32x32x16_bf16 per 16-deep k step
+//                waits in registers), six or nine v_mfma_f32_32x32x16_bf16 per 16-deep k step (NPROD)
 // The A operand always lies in LDS as above.  Where the exact step's B fragments come from is a B SOURCE, a callable of the
 // tile: (sn, kk) -> f32x4 gives the four k of this lane's half-wave for 32-pixel fragment sn and k group kk.  nt_mma_fp32 is the
 // instance that reads [row][kLds] rows; the flat forward tiles read shifted image rows and pixel-major images.  The split step
@@ -64,7 +64,7 @@ __device__ __forceinline__ void nt_mma_fp32(const float* As, const float* Bs, in
 
 // One chunk of the split images.  Lane (r, h) of k group g reads k = 16 g + 8 h .. + 7 of its row from each plane: the
 // operand map of the MFMA.
-template <int TM, int TN>
+template <int TM, int TN, int NPROD = 6>
 __device__ __forceinline__ void nt_mma_split(const __bf16* As16, const __bf16* Bs16, f32x16 (&acc)[TM / 64][TN / 64]) {
     constexpr int MTM = TM / 64, MTN = TN / 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
@@ -83,12 +83,12 @@ __device__ __forceinline__ void nt_mma_split(const __bf16* As16, const __bf16* B
 #pragma unroll
         for (int sm = 0; sm < MTM; ++sm)
 #pragma unroll
-            for (int sn = 0; sn < MTN; ++sn) acc[sm][sn] = split3_mfma(sa[sm], sb[sn], acc[sm][sn]);
+            for (int sn = 0; sn < MTN; ++sn) acc[sm][sn] = split3_mfma<NPROD>(sa[sm], sb[sn], acc[sm][sn]);
     }
 }
 
 // K chunks [c_begin, c_end): load(c) brings chunk c into registers, store(buf) masks it into LDS, compute(buf) multiplies.
-// The loads of chunk c + 1 stay in flight behind the MFMAs of chunk c.  SPLIT: one LDS image, so a second barrier (every
+// The loads of chunk c + 1 stay in flight behind the MFMAs of chunk c.  SPLIT (1 or 2): one LDS image, so a second barrier (every
 // wave is done reading it) comes before the store.
 template <int SPLIT, class Load, class Store, class Compute>
 __device__ __forceinline__ void nt_pipeline(int c_begin, int c_end, Load&& load, Store&& store, Compute&& compute) {

@@ -6,6 +6,7 @@ CUDA(=HIP) tensors; anything else raises -- there is no eager/CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import threading
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EPI_INNER, EPI_NEG_CDIST, PleasHipError, check
+from ._lib import ARITH_FP32, ARITH_SPLIT_BF16, ARITH_SPLIT_BF16_EXACT, EPI_INNER, EPI_NEG_CDIST, PleasHipError, check
 
 
 class _Pinned(threading.local):
@@ -958,6 +959,23 @@ def cholesky_solve_batched(As: Sequence[torch.Tensor], Bts: Sequence[torch.Tenso
         info.data_ptr(), _stream())
     check(rc, "pleas_cholesky_solve_batched")
     return info
+
+
+# ---------------------------------------------------------------------------------------- arithmetic of the contractions
+@contextlib.contextmanager
+def arith(mode: int):
+    """``pleas_arith(mode)`` for the block (``ARITH_FP32``, ``ARITH_SPLIT_BF16``: six of the nine bf16 products of every fp32
+    product, ``ARITH_SPLIT_BF16_EXACT``: all nine), the previous arithmetic again afterwards.  Process-wide, as the switch
+    itself: not for blocks that run beside other threads' launches.  Nothing in the package turns a split mode on."""
+    if mode not in (ARITH_FP32, ARITH_SPLIT_BF16, ARITH_SPLIT_BF16_EXACT):
+        raise PleasHipError("arith: unknown mode %r" % (mode,))
+    lib = _lib.lib()
+    before = lib.pleas_arith_get()
+    lib.pleas_arith(mode)
+    try:
+        yield
+    finally:
+        lib.pleas_arith(before)
 
 
 # ---------------------------------------------------------------------------------------- live kernel timing
