@@ -224,6 +224,27 @@ int pleas_bn_act_tracked_batches(const float* x, const float* scale, const float
 int pleas_bn_act_maxpool(const float* x, const float* scale, const float* shift, float* y, int64_t n, int channels, int H,
                          int W, int KH, int KW, int stride, int pad, int relu, void* stream);
 
+/* Head of an evaluation forward: global average pooling with an optional channel gather, one pass.
+ *
+ * Replaces: AdaptiveAvgPool2d((1, 1)) -> flatten(1) at the end of `model(x)` and, with a map, permute_final_features
+ *   (pleas/methods/pleas_merging.py:436-466: two slices, a cat and an index by argsort) in eval_perm_model (:469-496).
+ *   y[n][k] = (sum over p of x[n][src[k]][p]) / HW      x: [N][C][HW], y: [N][K] contiguous fp32
+ * src: DEVICE int32[K], entries in [0, C) -- they may repeat or reorder channels; the CALLER checks the range before the
+ *   launch (an entry outside it reads nothing and yields NaN);  NULL = identity, K == C.
+ * Fixed summation order, no atomics: the same bits run after run.  16-byte loads when HW % 4 == 0 and x is 16-byte aligned. */
+int pleas_pool_gather(const float* x, const int32_t* src, float* y, int64_t N, int C, int64_t HW, int K, void* stream);
+
+/* Top-1 accuracy counting on the device.
+ *
+ * Replaces: `logits.argmax(1)` + compare + sum of eval_perm_model (pleas/methods/pleas_merging.py:469-496, torchmetrics'
+ *   Accuracy) and the per-batch `.argmax(1).cpu()` of eval_whole_model (:574-586) -- one host synchronisation per batch there,
+ *   none here.
+ *   top[n] = the FIRST index of the largest value of logits[n][0 .. C) (torch.argmax's tie rule; a NaN counts as largest)
+ *   pred[n] = top[n] when pred != NULL;      *hits += number of rows with top[n] == labels[n]
+ * logits [N][C] contiguous fp32, labels / pred DEVICE int64[N], hits a DEVICE int64 (8-byte aligned) that the caller zeroes
+ * once and reads back once after its loop.  Integer atomics only: deterministic.  C = 1 and N = 1 are legal. */
+int pleas_top1_count(const float* logits, const int64_t* labels, int64_t N, int C, int64_t* hits, int64_t* pred, void* stream);
+
 /* Train-mode BatchNorm of the matching forward, folded to the same per-channel affine map.
  *
  * Replaces: the BatchNorm2d modules inside the cross module's forward when the caller's models are in train mode --
@@ -354,6 +375,17 @@ int pleas_conv2d_fwd(const float* x, const float* w, const float* bias, float* y
 int pleas_conv2d_bn_act_fwd(const float* x, const float* w, const float* bias, float* y, const float* scale,
                             const float* shift, const float* res, float* z, int relu, int N, int Cin, int Hin, int Win,
                             int Cout, int KH, int KW, int stride, int pad, int flags, void* stream);
+/* pleas_conv2d_act_fwd: the arithmetic of pleas_conv2d_bn_act_fwd with the activated image as its ONLY output:
+ *   z = act(fma(conv(x, w) (+ bias), scale[c], shift[c]) (+ res))
+ * -- bit for bit the z of pleas_conv2d_bn_act_fwd on the same inputs, under every pleas_arith mode and weight layout; y is
+ * neither an argument nor stored (a third of the output traffic of a 1 x 1 layer).
+ * Replaces: the Conv2d -> BatchNorm2d -> (+ identity) -> ReLU module chains of `model(x)` in the evaluation helpers
+ *   (pleas/methods/pleas_merging.py:469-496 eval_perm_model, :575-586 eval_whole_model, :499-570 the linear probe's frozen
+ *   backbone), where no hook reads the convolution's output.
+ * Same argument checks, alignment rules (x, w, z, res 16-byte aligned) and per-call size limits as its sibling. */
+int pleas_conv2d_act_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                         const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH, int KW,
+                         int stride, int pad, int flags, void* stream);
 typedef struct pleas_wgrad_layer {
     const float* resid; /* [N][Cout][Hout*Wout] */
     const float* ip;    /* [N][Cin][Hin][Win]   */

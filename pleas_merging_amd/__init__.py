@@ -8,4 +8,4 @@ compute is done by hand-written gfx950 HIP kernels behind the C-ABI declared in
 # of the frozen source / twin forwards -- the only ones whose vendor kernels mattered for parity -- run on the library's own kernel
 # since round 5 (methods/source_forward.py: SOURCE_CONV; PLEAS_SOURCE_CONV=vendor restores the vendor path).
 
-__version__ = "0.5.0"
+__version__ = "0.6.0"

@@ -53,7 +53,7 @@ struct FwdLayerDev {
     int variant;          // bit0: TM == 64, bit1: scalar W loads, bit2: W is kernel-position-major [Cout][KH*KW][Cin],
                           // bit3: flat-shift tile (fwd_flat_tile), bits 4-5: its KIND
     int part_base;        // first loss-partial slot of this layer
-    int bn_relu;          // PLAIN == 2: ReLU after the affine map (+ identity)
+    int bn_relu;          // PLAIN >= 2: ReLU after the affine map (+ identity)
     // PLAIN == 2 (pleas_conv2d_bn_act_fwd): the convolution's output goes to `resid` AND its activated image
     // z = act(y * bn_scale[co] + bn_shift[co] (+ bn_res)) to `bn_z` -- the BatchNorm / add / ReLU pass that follows a frozen
     // source's convolution, without reading y back from memory
@@ -61,6 +61,7 @@ struct FwdLayerDev {
     const float* bn_shift;   // [Cout]
     const float* bn_res;     // [N][Cout][HWo] or null
     float* bn_z;             // [N][Cout][HWo]
+    // PLAIN == 3 (pleas_conv2d_act_fwd): the same arithmetic, the activated image ALONE is stored (`resid` is null and unused)
 };
 struct FwdItemDev {
     int layer, tm, tp, slot;  // slot: loss-partial index
@@ -69,7 +70,7 @@ struct FwdItemDev {
 // ---- shared by both tile forms: the epilogue and its per-row operands.  A thread owns the TM / 8 output channels
 // tid / 32 + 8 j of its tile; per channel the epilogue takes two 32-bit values and the bias:
 //   PLAIN 0 / 1: the channel's rows in the two sources' outputs (the block maps; -1 = absent)
-//   PLAIN 2:     the channel's BatchNorm scale and shift (no block maps there)
+//   PLAIN 2 / 3: the channel's BatchNorm scale and shift (no block maps there)
 template <int TM, int PLAIN>
 struct FwdRowOps {
     int row1[TM / 8], row2[TM / 8];
@@ -80,13 +81,15 @@ struct FwdRowOps<TM, 2> {
     float scale[TM / 8], shift[TM / 8];
     float bias[TM / 8];
 };
+template <int TM>
+struct FwdRowOps<TM, 3> : FwdRowOps<TM, 2> {};
 template <int TM, int PLAIN = 0>
 __device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0, FwdRowOps<TM, PLAIN>& ops) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int j = 0; j < TM / 8; ++j) {
         const int co = min(i0 + (tid >> 5) + 8 * j, L.Cout - 1);
-        if constexpr (PLAIN == 2) {
+        if constexpr (PLAIN >= 2) {
             ops.scale[j] = PLEAS_GLOBAL(L.bn_scale)[co];
             ops.shift[j] = PLEAS_GLOBAL(L.bn_shift)[co];
         } else {
@@ -102,6 +105,8 @@ __device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0
 // PLAIN = 2 (pleas_conv2d_bn_act_fwd): the same, and the activated image  act(fma(y, scale, shift) + identity)  is stored
 // beside y -- the arithmetic of bn_act_kernel (elementwise.hip) on the value that is still in registers; the identity takes
 // the gather slots of the target
+// PLAIN = 3 (pleas_conv2d_act_fwd): PLAIN = 2 without the store of y -- a compile-time mode, so that the kernels of the other
+// modes stay the code they were
 template <int TM, int PLAIN = 0>
 __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItemDev& it, f32x16 (&acc)[TM / 64][2],
                                              const FwdRowOps<TM, PLAIN>& ops, float* smem, float* __restrict__ partials) {
@@ -146,8 +151,8 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
         const uint32_t gbase = 4u * (gn * (uint32_t)L.Csrc * L.HWo + gp);
         const uint32_t rbase = 4u * ((gn * (uint32_t)L.Cout + (uint32_t)i0 + (uint32_t)(tid >> 5)) * L.HWo + gp);
         // PLAIN == 2: the identity (shaped like the output) stands where the first source's outputs are gathered from
-        const bool has_res = PLAIN == 2 && L.bn_res != nullptr;
-        const char* o1b = reinterpret_cast<const char*>(PLAIN == 2 ? (has_res ? L.bn_res : L.ip) : L.o1);
+        const bool has_res = PLAIN >= 2 && L.bn_res != nullptr;
+        const char* o1b = reinterpret_cast<const char*>(PLAIN >= 2 ? (has_res ? L.bn_res : L.ip) : L.o1);
         const char* o2b = reinterpret_cast<const char*>(L.o2);
         char* rb_ = reinterpret_cast<char*>(L.resid);
         char* zb_ = reinterpret_cast<char*>(L.bn_z);
@@ -155,7 +160,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
 #pragma unroll
             for (int u = 0; u < GB; ++u) {
                 const int j = bt * GB + u;
-                if constexpr (PLAIN == 2) {
+                if constexpr (PLAIN >= 2) {
                     // unconditional load from a valid address (the output's own offset into the identity; the first floats
                     // of the input for rows / pixels outside the layer and when there is no identity -- then voided by a
                     // select): no branch around a load
@@ -179,7 +184,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const int j = bt * GB + u;
                 const int lco = (tid >> 5) + 8 * j, co = i0 + lco;
                 const bool live = gin && co < L.Cout;
-                if constexpr (PLAIN == 2) {
+                if constexpr (PLAIN >= 2) {
                     const f32x4 o = *reinterpret_cast<const f32x4*>(Ct + lco * EL + pg);
                     f32x4 y, z;
 #pragma unroll
@@ -189,7 +194,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                         z[e] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
                     }
                     if (live) {
-                        *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = y;
+                        if constexpr (PLAIN == 2) *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = y;
                         *(__attribute__((address_space(1))) f32x4*)(zb_ + (rbase + (uint32_t)(8 * j) * hw4)) = z;
                     }
                 } else {
@@ -229,11 +234,11 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const uint32_t Pe = Pg + e;
                 if (Pe >= L.Ptot) break;
                 const uint32_t n = Pe / L.HWo, p = Pe - n * L.HWo;
-                if constexpr (PLAIN == 2) {
+                if constexpr (PLAIN >= 2) {
                     const size_t at = ((size_t)n * L.Cout + co) * L.HWo + p;
                     const float y = o[e] + ops.bias[j];
                     const float sm = fmaf(y, ops.scale[j], ops.shift[j]) + (L.bn_res ? PLEAS_GLOBAL(L.bn_res)[at] : 0.f);
-                    PLEAS_GLOBAL_W(L.resid)[at] = y;
+                    if constexpr (PLAIN == 2) PLEAS_GLOBAL_W(L.resid)[at] = y;
                     PLEAS_GLOBAL_W(L.bn_z)[at] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
                 } else {
                     float a = 0.f, b = 0.f;
@@ -881,21 +886,22 @@ __global__ __launch_bounds__(kThreads, kFwdForms[FORM].occupancy[SPLIT]) void co
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const FwdItemDev it{0, (int)(blockIdx.x % (unsigned)tms), (int)(blockIdx.x / (unsigned)tms), 0};
     constexpr FwdForm F = kFwdForms[FORM];
-    constexpr int PLAIN = 1 + BN;      // 2: the BatchNorm / add / ReLU image is written beside the output
+    constexpr int PLAIN = 1 + BN;      // 2: the BatchNorm / add / ReLU image is written beside the output; 3: that image alone
     if constexpr (F.flat) fwd_flat_tile<F.tm, F.sub, SPLIT, PLAIN>(L, it, smem, nullptr);
     else fwd_tile<F.tm, F.sub, PLAIN>(L, it, smem, nullptr);
 }
 // The kernels of a form, [arithmetic = pleas_arith's mode]: a form without split kernels keeps its exact one there.
 struct FwdFormKernels {
     void (*batch[3])(const FwdLayerDev*, const FwdItemDev*, float*);
-    void (*conv2d[2][3])(const FwdLayerDev, const int);      // [BN][arithmetic]
+    void (*conv2d[3][3])(const FwdLayerDev, const int);      // [BN][arithmetic]; BN 2: image only
 };
 template <int FORM>
 static constexpr FwdFormKernels fwd_form_kernels() {
     constexpr int S = kFwdForms[FORM].split ? 1 : 0, S9 = kFwdForms[FORM].split ? 2 : 0;
     return {{fwd_batch_kernel<FORM, 0>, fwd_batch_kernel<FORM, S>, fwd_batch_kernel<FORM, S9>},
             {{conv2d_fwd_kernel<FORM, 0, 0>, conv2d_fwd_kernel<FORM, S, 0>, conv2d_fwd_kernel<FORM, S9, 0>},
-             {conv2d_fwd_kernel<FORM, 0, 1>, conv2d_fwd_kernel<FORM, S, 1>, conv2d_fwd_kernel<FORM, S9, 1>}}};
+             {conv2d_fwd_kernel<FORM, 0, 1>, conv2d_fwd_kernel<FORM, S, 1>, conv2d_fwd_kernel<FORM, S9, 1>},
+             {conv2d_fwd_kernel<FORM, 0, 2>, conv2d_fwd_kernel<FORM, S, 2>, conv2d_fwd_kernel<FORM, S9, 2>}}};
 }
 static const FwdFormKernels kFwdKernels[fForms] = {fwd_form_kernels<0>(), fwd_form_kernels<1>(), fwd_form_kernels<2>(), fwd_form_kernels<3>(),
                                                    fwd_form_kernels<4>(), fwd_form_kernels<5>(), fwd_form_kernels<6>(), fwd_form_kernels<7>(),
@@ -1162,13 +1168,15 @@ extern "C" size_t pleas_fwd_batch_ws_bytes(const pleas_fwd_layer* layers, int n_
     return tmp.total;
 }
 
-// y = conv(x, w) (+ bias); with `scale`: also z = act(y * scale[c] + shift[c] (+ res)) in the same epilogue
+// y = conv(x, w) (+ bias); with `scale`: also z = act(y * scale[c] + shift[c] (+ res)) in the same epilogue; `image_only`
+// (with `scale`): z alone, y is neither given nor stored
 static int conv2d_launch(const float* x, const float* w, const float* bias, float* y, const float* scale, const float* shift,
                          const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH, int KW,
-                         int stride, int pad, int flags, void* stream_) {
-    if (!x || !w || !y) return bad_arg("conv2d_fwd: null pointer");
+                         int stride, int pad, int flags, void* stream_, bool image_only = false) {
+    if (!x || !w || (!y && !image_only)) return bad_arg("conv2d_fwd: null pointer");
     if (((uintptr_t)w & 15) != 0 || ((uintptr_t)x & 15) != 0) return bad_arg("conv2d_fwd: x and w must be 16-byte aligned");
     const bool bn = scale != nullptr;
+    if (image_only && (!bn || y)) return bad_arg("conv2d_act_fwd: the image-only epilogue takes scale and no y");
     if (bn && (!shift || !z)) return bad_arg("conv2d_bn_act_fwd: scale needs shift and z");
     if (bn && ((((uintptr_t)y | (uintptr_t)z | (uintptr_t)res) & 15) != 0))
         return bad_arg("conv2d_bn_act_fwd: y, z and res must be 16-byte aligned");
@@ -1189,8 +1197,9 @@ static int conv2d_launch(const float* x, const float* w, const float* bias, floa
     hipStream_t st = (hipStream_t)stream_;
     const double out_floats = (double)Cout * d.Ptot;
     ProfScope prof(kProfConv2d, 2.0 * Cout * (double)d.Kd * (double)d.Ptot,
-                   ((double)Cin * N * Hin * Win + out_floats * (bn ? (res ? 3.0 : 2.0) : 1.0)) * sizeof(float), st);
-    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? 1 : 0][arith_mode()], grid, dim3(kThreads), lds, st, d, tms);
+                   ((double)Cin * N * Hin * Win + out_floats * ((bn && !image_only ? 2.0 : 1.0) + (res ? 1.0 : 0.0))) * sizeof(float), st);
+    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? (image_only ? 2 : 1) : 0][arith_mode()], grid, dim3(kThreads), lds, st,
+                       d, tms);
     PLEAS_LAUNCH_CHECK("conv2d_fwd_kernel");
     return PLEAS_OK;
 }
@@ -1206,6 +1215,14 @@ extern "C" int pleas_conv2d_bn_act_fwd(const float* x, const float* w, const flo
                                        int Win, int Cout, int KH, int KW, int stride, int pad, int flags, void* stream_) {
     if (!scale || !shift || !z) return bad_arg("conv2d_bn_act_fwd: null pointer");
     return conv2d_launch(x, w, bias, y, scale, shift, res, z, relu, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_);
+}
+
+extern "C" int pleas_conv2d_act_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                                    const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH,
+                                    int KW, int stride, int pad, int flags, void* stream_) {
+    if (!scale || !shift || !z) return bad_arg("conv2d_act_fwd: null pointer");
+    return conv2d_launch(x, w, bias, nullptr, scale, shift, res, z, relu, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_,
+                         true);
 }
 
 // The calibration launch's events: all complete?  Then the plan's units take their measured durations, long ones are cut and

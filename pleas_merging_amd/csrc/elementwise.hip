@@ -261,11 +261,92 @@ __global__ __launch_bounds__(64) void sqerr_final_kernel(const float* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Head of an evaluation forward: y[n][k] = mean over p of x[n][src[k]][p] -- AdaptiveAvgPool2d((1, 1)) + flatten and, with a
+// channel map, the gather of permute_final_features, in one pass over the channels that are read.  One wave per output:
+// lane l sums elements l, l + 64, ... of the row (16-byte pieces when VEC == 4), then a fixed xor tree over the lanes and one
+// division: the same bits run after run, no atomics.  A map entry outside [0, C) (refused by the callers before the launch)
+// reads nothing and yields NaN.
+template <int VEC>
+__global__ __launch_bounds__(kEwThreads) void pool_gather_kernel(const float* __restrict__ x, const int32_t* __restrict__ src,
+                                                                 float* __restrict__ y, int64_t rows, int C, int K, int64_t HW) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = (int64_t)blockIdx.x * (kEwThreads / 64) + (threadIdx.x >> 6);
+    for (int64_t row = wave0; row < rows; row += (int64_t)gridDim.x * (kEwThreads / 64)) {
+        const int64_t n = row / K;
+        const int k = (int)(row - n * K);
+        const int c = src ? src[k] : k;
+        if (c < 0 || c >= C) {            // wave-uniform
+            if (lane == 0) y[row] = __builtin_nanf("");
+            continue;
+        }
+        const float* in = x + (n * C + c) * HW;
+        float s = 0.f;
+        if constexpr (VEC == 4) {
+            const f32x4* in4 = reinterpret_cast<const f32x4*>(in);
+            for (int64_t i = lane; i < HW / 4; i += 64) {
+                const f32x4 v = in4[i];
+                s += (v[0] + v[1]) + (v[2] + v[3]);
+            }
+        } else {
+            for (int64_t i = lane; i < HW; i += 64) s += in[i];
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        if (lane == 0) y[row] = s / (float)HW;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Top-1 of every row of logits[N][C] and the count of rows whose top-1 is the label.  torch.argmax's rules: the FIRST maximal
+// index, a NaN is maximal.  One wave per row: lane l scans columns l, l + 64, ... (ascending, so only a strictly better value
+// replaces the lane's), then the (value, index) pairs go through an xor tree under the total order below.  Rows are dealt
+// to waves grid-strided; a workgroup adds its count with ONE 64-bit integer atomic (integers: any order gives the same sum).
+__device__ __forceinline__ bool top1_better(float va, int ia, float vb, int ib) {
+    const bool na = va != va, nb = vb != vb;
+    if (na != nb) return na;
+    if (!na && va != vb) return va > vb;
+    return ia < ib;
+}
+__global__ __launch_bounds__(kEwThreads) void top1_count_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                int64_t N, int C, unsigned long long* __restrict__ hits,
+                                                                int64_t* __restrict__ pred) {
+    __shared__ int wave_hits[kEwThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int mine = 0;                          // rows this wave got right (kept by lane 0)
+    for (int64_t row = (int64_t)blockIdx.x * (kEwThreads / 64) + wave; row < N; row += (int64_t)gridDim.x * (kEwThreads / 64)) {
+        const float* in = logits + row * C;
+        float bv = -__builtin_inff();
+        int bi = 0x7fffffff;               // a lane without columns: loses every tie against a real column
+        for (int i = lane; i < C; i += 64) {
+            const float v = in[i];
+            if (top1_better(v, i, bv, bi)) { bv = v; bi = i; }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float ov = __shfl_xor(bv, off);
+            const int oi = __shfl_xor(bi, off);
+            if (top1_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) {
+            if (pred) pred[row] = bi;
+            mine += labels[row] == (int64_t)bi ? 1 : 0;
+        }
+    }
+    if (lane == 0) wave_hits[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < kEwThreads / 64; ++w) t += wave_hits[w];
+        if (t) atomicAdd(hits, (unsigned long long)t);
+    }
+}
+
 }  // namespace pleas
 
 using namespace pleas;
 
-extern "C" const char* pleas_version(void) { return "pleas_hip 0.5.0 gfx950"; }
+extern "C" const char* pleas_version(void) { return "pleas_hip 0.6.0 gfx950"; }
 extern "C" const char* pleas_last_error(void) { return g_last_error; }
 
 // ---- arithmetic of the contraction kernels: -1 = not decided yet (PLEAS_ARITH read once), 0 = exact fp32 MFMA, 1 = split bf16
@@ -542,5 +623,36 @@ extern "C" int pleas_channel_sum(const float* x, int N, int C, int64_t HW, float
     if (N <= 0 || C <= 0 || HW <= 0) return bad_arg("channel_sum: empty tensor");
     hipLaunchKernelGGL(channel_sum_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream_, x, N, C, (long long)HW, out);
     PLEAS_LAUNCH_CHECK("channel_sum_kernel");
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_pool_gather(const float* x, const int32_t* src, float* y, int64_t N, int C, int64_t HW, int K, void* stream_) {
+    if (!x || !y) return bad_arg("pool_gather: null pointer");
+    if (N < 0 || C <= 0 || HW <= 0 || K <= 0) return bad_arg("pool_gather: empty tensor");
+    if (!src && K != C) return bad_arg("pool_gather: K != C without a channel map");
+    const int64_t rows = N * K;
+    if (rows == 0) return PLEAS_OK;
+    if (rows >= ((int64_t)1 << 40) || N * C >= ((int64_t)1 << 40)) return bad_arg("pool_gather: tensor too large");
+    hipStream_t stream = (hipStream_t)stream_;
+    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(rows, kEwThreads / 64), (int64_t)1 << 20);
+    ProfScope prof(kProfBnAct, 0.0, ((double)rows * HW + (double)rows) * sizeof(float), stream);
+    if (HW % 4 == 0 && ((uintptr_t)x & 15) == 0)
+        hipLaunchKernelGGL((pool_gather_kernel<4>), dim3(grid), dim3(kEwThreads), 0, stream, x, src, y, rows, C, K, HW);
+    else
+        hipLaunchKernelGGL((pool_gather_kernel<1>), dim3(grid), dim3(kEwThreads), 0, stream, x, src, y, rows, C, K, HW);
+    PLEAS_LAUNCH_CHECK("pool_gather_kernel");
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_top1_count(const float* logits, const int64_t* labels, int64_t N, int C, int64_t* hits, int64_t* pred,
+                                void* stream_) {
+    if (!logits || !labels || !hits) return bad_arg("top1_count: null pointer");
+    if (N < 0 || C <= 0) return bad_arg("top1_count: empty rows");
+    if (N == 0) return PLEAS_OK;
+    if (((uintptr_t)hits & 7) != 0) return bad_arg("top1_count: hits must be 8-byte aligned");
+    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(N, kEwThreads / 64), kEwMaxBlocks);
+    hipLaunchKernelGGL(top1_count_kernel, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream_, logits, labels, N, C,
+                       reinterpret_cast<unsigned long long*>(hits), pred);
+    PLEAS_LAUNCH_CHECK("top1_count_kernel");
     return PLEAS_OK;
 }

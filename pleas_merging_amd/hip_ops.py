@@ -849,6 +849,123 @@ def conv2d_bn_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
     return y, z
 
 
+# per-call limits of the convolution kernels (fwd_describe, csrc/conv_fwd.hip): fewer than 2^30 output elements and fewer than
+# 2^31 output pixels over the batch
+CONV_MAX_OUTPUT, CONV_MAX_PIXELS = 1 << 30, 1 << 31
+
+
+def conv2d_sample_split(N: int, per_sample_out: int, pixels: int, limit: int = CONV_MAX_OUTPUT, align: int = 1) -> List[Tuple[int, int]]:
+    """``[(first sample, samples)]`` of the FEWEST calls that each stay under the per-call limits (``samples * per_sample_out
+    < limit``, ``samples * pixels < 2^31``), sizes as equal as possible (they differ by at most ``align``, larger ones first).
+    ``align``: every call but the last starts and ends on a multiple of it (the sample count that keeps slices 16-byte
+    aligned).  Host arithmetic only.  One sample that does not fit is refused."""
+    if N <= 0:
+        return []
+    most = min((limit - 1) // per_sample_out, (CONV_MAX_PIXELS - 1) // pixels) // align * align
+    if most <= 0:
+        raise PleasHipError("conv2d_act: one sample (%d output elements, %d pixels) exceeds the per-call limit" % (per_sample_out, pixels))
+    groups = -(-N // align)
+    calls = -(-groups // (most // align))
+    base, extra = divmod(groups, calls)
+    parts, at = [], 0
+    for i in range(calls):
+        n = min((base + (1 if i < extra else 0)) * align, N - at)
+        parts.append((at, n))
+        at += n
+    return parts
+
+
+def conv2d_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int, kpos_major: bool,
+               scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor], relu: bool,
+               _limit: int = CONV_MAX_OUTPUT) -> torch.Tensor:
+    """``z = bn_act(conv2d(x, w, bias), scale, shift, res, relu)`` with z as the ONLY output (``pleas_conv2d_act_fwd``): bit for
+    bit the ``z`` of ``conv2d_bn_act``, the convolution's own output is never written.  For forwards nobody hooks (evaluation).
+    A batch whose output crosses the per-call limit of the kernels is split along the sample axis (``conv2d_sample_split``)
+    into calls that write one ``z``.  ``_limit``: the output-element limit, for tests."""
+    _need_gpu(x, w, scale, shift)
+    N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d_act", x, w, stride, pad, kpos_major)
+    if scale.numel() != Cout or shift.numel() != Cout or not scale.is_contiguous() or not shift.is_contiguous():
+        raise PleasHipError("conv2d_act: scale / shift must be contiguous fp32 vectors of %d channels" % Cout)
+    if res is not None and (tuple(res.shape) != (N, Cout, Ho, Wo) or res.dtype != torch.float32 or not res.is_contiguous()
+                            or res.device != x.device):
+        raise PleasHipError("conv2d_act: the identity must be a contiguous fp32 tensor shaped like the output")
+    z = torch.empty((N, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    if N == 0 or Ho <= 0 or Wo <= 0:
+        return z
+    per_out, per_in = Cout * Ho * Wo, Cin * H * W
+    if N * per_out < _limit and N * Ho * Wo < CONV_MAX_PIXELS:
+        parts = [(0, N)]
+    else:
+        # slices of x, z and the identity must start 16-byte aligned: whole groups of `align` samples
+        align = max(4 // math.gcd(4, per_out), 4 // math.gcd(4, per_in))
+        parts = conv2d_sample_split(N, per_out, Ho * Wo, _limit, align)
+    fn, flags, st = _lib.lib().pleas_conv2d_act_fwd, FwdBatch.KPOS_MAJOR if kpos_major else 0, _stream()
+    for at, n in parts:
+        check(fn(x[at:at + n].data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, scale.data_ptr(),
+                 shift.data_ptr(), res[at:at + n].data_ptr() if res is not None else None, z[at:at + n].data_ptr(),
+                 1 if relu else 0, n, Cin, H, W, Cout, KH, KW, stride, pad, flags, st), "pleas_conv2d_act_fwd")
+    return z
+
+
+def channel_map(index, channels: int, device) -> torch.Tensor:
+    """A channel map for ``pool_gather``: ``index`` (any integer sequence / tensor) as a contiguous int32 tensor on ``device``,
+    its entries checked against ``[0, channels)`` on the HOST, once -- ``pool_gather`` takes it without looking again."""
+    idx = torch.as_tensor(index).detach().to("cpu", torch.int64).reshape(-1)
+    if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= channels:
+        raise PleasHipError("channel_map: entries must lie in [0, %d) and the map must not be empty" % channels)
+    src = idx.to(torch.int32).to(device).contiguous()
+    src._pleas_channels = channels
+    return src
+
+
+def pool_gather(x: torch.Tensor, src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y[n, k] = mean over the pixels of x[n, src[k]]`` for ``x`` [N, C, ...] (``pleas_pool_gather``): ``AdaptiveAvgPool2d((1, 1))``
+    + ``flatten(1)`` and, with ``src`` (int32 device vector; entries may repeat or reorder), the gather of
+    ``permute_final_features`` in the same pass.  Fixed summation order: the same bits run after run.  A map not made by
+    ``channel_map`` is range-checked here (one read-back); an entry outside ``[0, C)`` is refused."""
+    _need_gpu(x)
+    if x.dim() < 2:
+        raise PleasHipError("pool_gather needs an fp32 [N, C, ...] tensor")
+    x = x.contiguous()
+    N, C = x.shape[0], x.shape[1]
+    HW = math.prod(x.shape[2:])
+    K = C
+    if src is not None:
+        if not src.is_cuda or src.device != x.device or src.dtype != torch.int32 or src.dim() != 1 or not src.is_contiguous() or src.numel() == 0:
+            raise PleasHipError("pool_gather: the channel map must be a non-empty contiguous int32 vector on x's device")
+        if getattr(src, "_pleas_channels", None) != C:
+            lo, hi = (int(v) for v in torch.aminmax(src))
+            if lo < 0 or hi >= C:
+                raise PleasHipError("pool_gather: channel map entries must lie in [0, %d), got [%d, %d]" % (C, lo, hi))
+        K = src.numel()
+    y = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    if N == 0:
+        return y
+    if HW == 0:
+        raise PleasHipError("pool_gather: empty images")
+    check(_lib.lib().pleas_pool_gather(x.data_ptr(), src.data_ptr() if src is not None else None, y.data_ptr(), N, C, HW, K,
+                                       _stream()), "pleas_pool_gather")
+    return y
+
+
+def top1_count(logits: torch.Tensor, labels: torch.Tensor, hits: torch.Tensor, pred: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hits += number of rows n with argmax(logits[n]) == labels[n]`` on the device, no synchronisation
+    (``pleas_top1_count``): the first maximal index wins, a NaN counts as maximal (``torch.argmax``).  ``logits`` [N, C] fp32,
+    ``labels`` / ``pred`` int64 [N], ``hits`` a one-element int64 device tensor the caller zeroes once and reads once;
+    ``pred`` (optional) receives the predictions.  Returns ``hits``."""
+    _need_gpu(logits)
+    if logits.dim() != 2 or not logits.is_contiguous() or logits.shape[1] < 1:
+        raise PleasHipError("top1_count: logits must be a contiguous [N, C] tensor with C >= 1")
+    N, C = logits.shape
+    for name, t, n in (("labels", labels, N), ("hits", hits, 1)) + ((("pred", pred, N),) if pred is not None else ()):
+        if t.device != logits.device or t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous():
+            raise PleasHipError("top1_count: %s must be a contiguous int64 tensor of %d element(s) on the logits' device" % (name, n))
+    if N:
+        check(_lib.lib().pleas_top1_count(logits.data_ptr(), labels.data_ptr(), N, C, hits.data_ptr(),
+                                          pred.data_ptr() if pred is not None else None, _stream()), "pleas_top1_count")
+    return hits
+
+
 class WgradBatch(_GroupedLaunch):
     """Weight gradients of all merged layers of one update in ONE grouped launch (``pleas_wgrad_batch``).
     ``add`` per layer (operands must stay unmodified until ``flush``), ``flush`` once per update."""

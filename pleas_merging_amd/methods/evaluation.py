@@ -3,6 +3,13 @@ the block layout ``[merged | separate-of-model-1 | separate-of-model-2]`` that `
 
 Reference: pleas/methods/pleas_merging.py:408-496 (``get_fc_perm``, ``permute_final_features``, ``eval_perm_model``)
 and :575-586 (``eval_whole_model``).  Accuracy is counted directly (torchmetrics is not a dependency here).
+
+``backbone="modules"`` (default) is ``model(x)`` on the vendor's modules, as the reference runs it.  ``backbone="hip"`` runs the
+model as its inference graph on the library's own kernels (``source_forward.InferenceBackbone``: image-only convolutions with
+the BatchNorm / add / ReLU chain in their epilogue, one ``pool_gather`` for pooling + ``permute_final_features``, the head as an
+own Linear) and counts with ``hip_ops.top1_count`` into one device counter read back once after the loop; host batches are
+copied on the current stream without blocking the host.  It needs the model on the GPU (``PleasHipError`` otherwise) and a forward that no
+hook has to observe bit-for-bit in the vendor's arithmetic; hooks on convolutions still receive their outputs.
 """
 from __future__ import annotations
 
@@ -11,8 +18,12 @@ from typing import Iterable
 import torch
 from torch import nn
 
+from .. import hip_ops
 from ..core.utils import Axis, Permutation, PermutationSpec
 from .partial_matching import get_blocks
+from .source_forward import HipLinear, InferenceBackbone
+
+BACKBONES = ("modules", "hip")
 
 
 def get_fc_perm(perm: Permutation, spec: PermutationSpec, costs, budget_ratios):
@@ -38,12 +49,62 @@ def permute_final_features(features: torch.Tensor, fc_perm, idx: int) -> torch.T
     return torch.cat([merged, own], 1)[:, torch.argsort(order).to(features.device)]
 
 
+def final_feature_map(fc_perm, idx: int) -> torch.Tensor:
+    """``permute_final_features`` as ONE gather: the int64 CPU vector ``src`` with
+    ``permute_final_features(f, fc_perm, idx) == f[:, src]`` for every feature matrix ``f`` of the merged backbone."""
+    b1, b2, b1c, b2c = (b.cpu() for b in fc_perm)
+    ni, mi = len(b1), len(b1c)
+    own = torch.arange(ni, ni + mi) + (0 if idx == 0 else mi)           # where the [merged | own] columns sit in f
+    order = torch.cat([b1, b1c], 0) if idx == 0 else torch.cat([b2, b2c], 0)
+    return torch.cat([torch.arange(ni), own], 0)[torch.argsort(order)]
+
+
+def _hip_backbone(model: nn.Module, backbone: str):
+    """``(device, InferenceBackbone or None)`` for the ``backbone`` keyword of the helpers."""
+    if backbone not in BACKBONES:
+        raise ValueError("backbone must be one of %r, got %r" % (BACKBONES, backbone))
+    device = next(iter(model.parameters())).device
+    if backbone == "modules":
+        return device, None
+    if device.type != "cuda":
+        raise hip_ops.PleasHipError('backbone="hip" needs the model on the GPU (got %s); no CPU fallback' % device)
+    return device, InferenceBackbone(model)
+
+
+def _device_batches(dataloader: Iterable, device: torch.device):
+    """``(x, y)`` on ``device``, copied on the CURRENT stream without blocking the host (``non_blocking``: asynchronous for
+    pinned host tensors, in stream order with the kernels that read them)."""
+    move = lambda t: t.to(device, non_blocking=True) if isinstance(t, torch.Tensor) else t
+    for x, y in dataloader:
+        yield move(x), move(y)
+
+
+def _labels(y: torch.Tensor) -> torch.Tensor:
+    return y.reshape(-1).to(torch.int64).contiguous()
+
+
 @torch.no_grad()
-def eval_perm_model(model: nn.Module, fc: nn.Module, dataloader: Iterable, num_classes: int, fc_perm, idx: int) -> torch.Tensor:
+def eval_perm_model(model: nn.Module, fc: nn.Module, dataloader: Iterable, num_classes: int, fc_perm, idx: int,
+                    backbone: str = "modules") -> torch.Tensor:
     """Top-1 accuracy of the merged backbone under the classifier of source model ``idx``.  Reference :469-496
     (``num_classes`` is kept for the signature; the count does not need it)."""
-    device = next(iter(model.parameters())).device
+    device, hip = _hip_backbone(model, backbone)
     model.eval()
+    if hip is not None:
+        src = final_feature_map(fc_perm, idx)
+        head = HipLinear(fc, "fc") if type(fc) is nn.Linear else fc
+        # the merged backbone emits [merged | separate-1 | separate-2]; the map is checked against that width on the host, once
+        smap = hip_ops.channel_map(src, len(fc_perm[0]) + 2 * len(fc_perm[2]), device)
+        in_graph = hip.gather_features(smap)      # else: a graph that does not end in its pooling pass -- gathered below
+        hit = torch.zeros(1, dtype=torch.long, device=device)
+        seen = 0
+        for x, y in _device_batches(dataloader, device):
+            feats = hip(x)
+            if not in_graph:
+                feats = hip_ops.pool_gather(feats.reshape(feats.shape[0], -1, 1), smap)
+            hip_ops.top1_count(head(feats).contiguous(), _labels(y), hit)
+            seen += int(y.numel())
+        return hit[0].float() / max(seen, 1)
     hit = torch.zeros((), dtype=torch.long, device=device)
     seen = 0
     for x, y in dataloader:
@@ -55,11 +116,19 @@ def eval_perm_model(model: nn.Module, fc: nn.Module, dataloader: Iterable, num_c
 
 
 @torch.no_grad()
-def eval_whole_model(model: nn.Module, dataloader: Iterable, num_classes: int) -> torch.Tensor:
+def eval_whole_model(model: nn.Module, dataloader: Iterable, num_classes: int, backbone: str = "modules") -> torch.Tensor:
     """Top-1 accuracy of a model with its own head.  Reference :575-586."""
-    device = next(iter(model.parameters())).device
+    device, hip = _hip_backbone(model, backbone)
     model.eval()
     hit, seen = 0, 0
+    if hip is not None:
+        hits = torch.zeros(1, dtype=torch.long, device=device)
+        for x, y in _device_batches(dataloader, device):
+            hip_ops.top1_count(hip(x).contiguous(), _labels(y), hits)
+            seen += int(y.numel())
+        acc = torch.tensor(int(hits[0]) / max(seen, 1))       # the loop's one read-back
+        print(acc)
+        return acc
     for x, y in dataloader:
         pred = model(x.to(device)).argmax(1).cpu()
         hit += int((pred == y.cpu()).sum())
@@ -70,17 +139,20 @@ def eval_whole_model(model: nn.Module, dataloader: Iterable, num_classes: int) -
 
 
 def train_eval_linear_probe(model: nn.Module, train_dataloader, test_dataloader, num_classes: int, wandb_run, dataset_name: str,
-                            lr: float = 1e-3, epochs: int = 10, device=None) -> nn.Module:
+                            lr: float = 1e-3, epochs: int = 10, device=None, backbone: str = "modules") -> nn.Module:
     """Linear probe on a frozen (merged) backbone, as the different-label-space driver evaluates merged models
     (reference :499-570; run_torchvision.py:276-290).  Same recipe: Adam(``lr``) on a fresh ``Linear`` head, cosine
     schedule over ``epochs * len(train_dataloader)`` steps down to ``lr / 10``, cross entropy, backbone in eval mode
     under ``no_grad``; per-epoch train accuracy / loss and the final test accuracy go to ``wandb_run.log`` under the
     reference's keys (``wandb_run=None`` skips logging).  Returns the trained head.  The backbone stays where it is
     (``device`` defaults to its device) -- the reference hard-codes ``.cuda()`` and a 224x224 probe input; here the
-    feature width is read from the first training batch."""
+    feature width is read from the first training batch.  ``backbone="hip"`` moves the frozen backbone's forwards to the
+    library's kernels; the head's Adam / cross entropy stay on autograd."""
+    own_device, hip = _hip_backbone(model, backbone)
     if device is None:
-        device = next(iter(model.parameters())).device
+        device = own_device
     model.eval()
+    features = hip if hip is not None else model
     n_batches = len(train_dataloader)
     fc = opt = sched = None
     loss_fn = nn.CrossEntropyLoss()
@@ -91,7 +163,7 @@ def train_eval_linear_probe(model: nn.Module, train_dataloader, test_dataloader,
         for x, y in train_dataloader:
             x, y = x.to(device), y.to(device)
             with torch.no_grad():
-                feats = model(x)
+                feats = features(x)
             if fc is None:
                 fc = nn.Linear(feats.shape[-1], num_classes).to(device)
                 opt = torch.optim.Adam(fc.parameters(), lr=lr)
@@ -116,7 +188,7 @@ def train_eval_linear_probe(model: nn.Module, train_dataloader, test_dataloader,
     with torch.no_grad():
         for x, y in test_dataloader:
             x, y = x.to(device), y.to(device)
-            hit += (fc(model(x)).argmax(1) == y).sum()
+            hit += (fc(features(x)).argmax(1) == y).sum()
             seen += int(y.numel())
     log({"%s_linear_probe_acc" % dataset_name: float(hit) / max(seen, 1)})
     return fc

@@ -115,11 +115,15 @@ class HipConvBnAct:
         self.own = own
         self.__name__ = self.__qualname__ = own.__name__ + "_bn_act"
 
+    def _fused_ok(self, x, scale, res) -> bool:
+        conv = self.own.conv
+        return not (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not conv.weight.is_cuda or scale.dim() != 1
+                    or (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad))
+                    or (res is not None and (not res.is_contiguous() or res.dtype != torch.float32 or res.data_ptr() % 16)))
+
     def __call__(self, x, scale, shift, res, relu):
         own, conv = self.own, self.own.conv
-        if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not conv.weight.is_cuda or scale.dim() != 1
-                or (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad))
-                or (res is not None and (not res.is_contiguous() or res.dtype != torch.float32 or res.data_ptr() % 16))):
+        if not self._fused_ok(x, scale, res):
             return _bn_act(own(x), scale, shift, res, relu)
         y, z = hip_ops.conv2d_bn_act(x if x.is_contiguous() else x.contiguous(), own.weight(), conv.bias, own.stride, own.pad,
                                      own.kpos, scale, shift, res, relu)
@@ -129,6 +133,116 @@ class HipConvBnAct:
                 if out is not None:
                     y, z = out, None
         return z if z is not None else _bn_act(y, scale, shift, res, relu)
+
+
+class HipConvAct(HipConvBnAct):
+    """The image-only form of ``HipConvBnAct`` for forwards nobody taps (evaluation): ``hip_ops.conv2d_act`` stores the
+    activated image and nothing else.  A convolution that carries forward hooks AT CALL TIME still owes them its output:
+    that call takes the two-output path of the parent class, as does everything the fused kernel does not take."""
+
+    def __init__(self, own: HipConv):
+        super().__init__(own)
+        self.__name__ = self.__qualname__ = own.__name__ + "_act"
+
+    def __call__(self, x, scale, shift, res, relu):
+        own, conv = self.own, self.own.conv
+        if (own.fire_hooks and conv._forward_hooks) or not self._fused_ok(x, scale, res):
+            return super().__call__(x, scale, shift, res, relu)
+        return hip_ops.conv2d_act(x if x.is_contiguous() else x.contiguous(), own.weight(), conv.bias, own.stride, own.pad,
+                                  own.kpos, scale, shift, res, relu)
+
+
+class PoolGather:
+    """Graph callable of the head: ``AdaptiveAvgPool2d((1, 1))`` -> ``flatten(1)`` as ONE ``hip_ops.pool_gather``.  ``src`` (a
+    ``hip_ops.channel_map``, or None) also gathers / reorders the pooled channels in the same pass -- what
+    ``permute_final_features`` does to the merged backbone's features.  CPU tensors take the two calls it replaces."""
+
+    def __init__(self):
+        self.src = None
+        self.__name__ = self.__qualname__ = "pool_gather"
+
+    def __call__(self, x):
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+            y = torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
+            return y if self.src is None else y[:, self.src.long()]
+        return hip_ops.pool_gather(x, self.src)
+
+
+class HipLinear:
+    """Graph callable standing in for an ``nn.Linear`` on 2-D features: ``hip_ops.conv2d`` with H = W = KH = KW = 1 on views
+    (no copy of the weight: the parameter is read where it is).  The module itself for anything else."""
+
+    def __init__(self, fc: nn.Linear, tag: str):
+        self.fc = fc
+        self.__name__ = self.__qualname__ = "hip_linear_%s" % tag
+
+    def __call__(self, x):
+        fc = self.fc
+        w = fc.weight
+        if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or not w.is_cuda or w.dtype != torch.float32
+                or not w.is_contiguous() or w.data_ptr() % 16
+                or (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
+            return fc(x)
+        x = x if x.is_contiguous() and x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
+        y = hip_ops.conv2d(x.view(x.shape[0], x.shape[1], 1, 1), w.detach().view(w.shape[0], w.shape[1], 1, 1), fc.bias, 1, 0)
+        return y.view(x.shape[0], w.shape[0])
+
+
+def _is_global_avgpool(node: torch.fx.Node, mods) -> bool:
+    one = lambda v: v in (1, (1, 1), [1, 1])
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        m = mods.get(node.target)
+        return type(m) is nn.AdaptiveAvgPool2d and one(m.output_size)
+    if node.op == "call_function" and node.target is F.adaptive_avg_pool2d and isinstance(node.args[0], torch.fx.Node):
+        size = node.args[1] if len(node.args) > 1 else node.kwargs.get("output_size")
+        return len(node.args) + len(node.kwargs) == 2 and one(size)
+    return False
+
+
+def _is_flatten1(node: torch.fx.Node, mods) -> bool:
+    """``flatten(x, 1)`` in one of its three spellings (on a [N, C, 1, 1] tensor an end_dim of -1 or 3 is the same)."""
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        m = mods.get(node.target)
+        return type(m) is nn.Flatten and m.start_dim == 1 and m.end_dim in (-1, 3)
+    if (node.op == "call_function" and node.target is torch.flatten) or (node.op == "call_method" and node.target == "flatten"):
+        rest = tuple(node.args[1:])
+        start = rest[0] if rest else node.kwargs.get("start_dim", 0)
+        end = rest[1] if len(rest) > 1 else node.kwargs.get("end_dim", -1)
+        return start == 1 and end in (-1, 3) and len(rest) + len(node.kwargs) <= 2
+    return False
+
+
+def _inference_passes(graph: torch.fx.Graph, mods) -> None:
+    """The rewrites of ``fuse_bn_act(.., inference=True)`` on top of the default graph: image-only convolutions, the fused
+    head, the own Linear behind it, no ``nn.Identity``."""
+    for node in list(graph.nodes):
+        if node.op == "call_function" and type(node.target) is HipConvBnAct:
+            own = node.target.own
+            with graph.inserting_before(node):
+                image = graph.create_node("call_function", HipConvAct(own), node.args, {}, name=own.__name__[len("hip_conv_"):] + "_hip_act")
+            node.replace_all_uses_with(image)
+            graph.erase_node(node)
+        elif node.op == "call_module" and type(mods.get(node.target)) is nn.Identity and len(node.args) == 1 and not node.kwargs:
+            node.replace_all_uses_with(node.args[0])
+            graph.erase_node(node)
+    for node in list(graph.nodes):
+        if not (_is_global_avgpool(node, mods) and len(node.users) == 1):
+            continue
+        flat = next(iter(node.users))
+        if not _is_flatten1(flat, mods) or flat.args[0] is not node:
+            continue
+        with graph.inserting_before(flat):
+            head = graph.create_node("call_function", PoolGather(), (node.args[0],), {}, name="pool_gather")
+        flat.replace_all_uses_with(head)
+        graph.erase_node(flat)
+        graph.erase_node(node)
+        for user in list(head.users):
+            fc = mods.get(user.target) if user.op == "call_module" else None
+            if type(fc) is nn.Linear and len(user.args) == 1 and not user.kwargs and fc.weight.dtype == torch.float32:
+                with graph.inserting_before(user):
+                    own = graph.create_node("call_function", HipLinear(fc, user.name), (head,), {}, name=user.name + "_hip")
+                user.replace_all_uses_with(own)
+                graph.erase_node(user)
 
 
 def _bn_act_pool(x, scale, shift, kernel, stride, padding, relu):
@@ -224,7 +338,8 @@ def _train_fold(bn: nn.BatchNorm2d, tag: str, state: Optional[BatchesPerForward]
 
 
 def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = False,
-                pool_op: Optional[Callable] = None, conv: Optional[str] = None) -> Optional[torch.fx.GraphModule]:
+                pool_op: Optional[Callable] = None, conv: Optional[str] = None,
+                inference: bool = False) -> Optional[torch.fx.GraphModule]:
     """fx copy of ``model`` (sharing its submodules) with every eval-mode BatchNorm2d chain replaced by
     ``op(x, scale, shift, residual_or_None, relu)`` -- the HIP kernel ``hip_ops.bn_act`` unless a test
     passes its own.  Returns None when the model cannot be traced or holds nothing to fold; the caller
@@ -239,7 +354,12 @@ def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = Fa
     pooling (``hip_ops.bn_act_maxpool`` with the default ``op``; with a caller's ``op`` only when passed too).
 
     ``conv`` ("kxk" / "all" / "vendor", default ``SOURCE_CONV``): which Conv2d calls become ``HipConv`` calls -- only with
-    the default ``op`` (a test's CPU ``op`` keeps the modules) and never for a model in train mode (autograd may be on)."""
+    the default ``op`` (a test's CPU ``op`` keeps the modules) and never for a model in train mode (autograd may be on).
+
+    ``inference=True`` (default ``op``, model in eval mode): the graph of a forward that nobody taps -- every ``HipConvBnAct``
+    becomes the image-only ``HipConvAct`` (a convolution that carries hooks when it is called still hands them its output),
+    ``AdaptiveAvgPool2d((1, 1))`` -> ``flatten(1)`` becomes one ``PoolGather``, an ``nn.Linear`` on its result the own
+    ``HipLinear``, and ``nn.Identity`` calls are dropped.  The stem and whatever is not recognised stay as in the default graph."""
     if pool_op is None and op is _bn_act:
         pool_op = _bn_act_pool
     try:
@@ -322,6 +442,8 @@ def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = Fa
                 node.replace_all_uses_with(both)
                 graph.erase_node(node)
                 graph.erase_node(src)
+        if inference:
+            _inference_passes(graph, mods)
     if folded == 0:
         return None
     graph.lint()
@@ -367,3 +489,38 @@ def uses_batch_statistics(gm) -> bool:
             if use_input is not False:
                 return True
     return False
+
+
+class InferenceBackbone:
+    """A frozen model as its inference graph (``fuse_bn_act(model, inference=True)``), called under ``no_grad``.  The folded
+    BatchNorm constants and the kernel-position-major weight copies are taken when the graph is built: after
+    ``reset_bn_stats``, ``load_state_dict`` or ``.data`` edits call ``refresh()``.  The model is put in eval mode (the graph is
+    an evaluation forward).  A model that cannot be traced runs as its modules."""
+
+    def __init__(self, model: nn.Module, conv: Optional[str] = None):
+        self.model, self.conv = model, conv
+        self.refresh()
+
+    def refresh(self) -> "InferenceBackbone":
+        self.model.eval()
+        self.graph = fuse_bn_act(self.model, conv=self.conv, inference=True)
+        self._head = None
+        if self.graph is not None:
+            heads = [n for n in self.graph.graph.nodes if n.op == "call_function" and isinstance(n.target, PoolGather)]
+            out = next(n for n in self.graph.graph.nodes if n.op == "output")
+            # the pooled features ARE the result (a backbone whose fc is Identity): a channel map may ride in the pooling pass
+            if len(heads) == 1 and out.args[0] is heads[0]:
+                self._head = heads[0].target
+        return self
+
+    def gather_features(self, src: Optional[torch.Tensor]) -> bool:
+        """Let the graph's pooling pass emit channels ``src`` (a ``hip_ops.channel_map``; None: all, in order).  False when
+        the graph does not end in its pooling pass -- the caller then gathers the result itself."""
+        if self._head is None:
+            return False
+        self._head.src = src
+        return True
+
+    @torch.no_grad()
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        return (self.graph if self.graph is not None else self.model)(x)
