@@ -245,6 +245,26 @@ int pleas_pool_gather(const float* x, const int32_t* src, float* y, int64_t N, i
  * once and reads back once after its loop.  Integer atomics only: deterministic.  C = 1 and N = 1 are legal. */
 int pleas_top1_count(const float* logits, const int64_t* labels, int64_t N, int C, int64_t* hits, int64_t* pred, void* stream);
 
+/* Softmax cross-entropy of a classification head: loss, gradient of the logits and the top-1 hit count from one pass.
+ *
+ * Replaces: nn.CrossEntropyLoss()(logits, y), its backward down to the logits, and `(logits.argmax(1) == y).sum()` of the
+ *   linear probe's training step (pleas/methods/pleas_merging.py:499-570) -- log_softmax, nll_loss, their two backward
+ *   kernels, argmax, compare, sum, and the `float(loss)` read-back per step there; no host synchronisation here.
+ *   per row n:  m = max_c x_c;  lse = m + log(sum_c exp(x_c - m));  row_loss[n] = lse - x[labels[n]]
+ *               dlogits[n][c] = scale * (exp(x_c - lse) - [c == labels[n]])            (skipped when dlogits == NULL)
+ *   loss[0] = scale * sum_n row_loss[n];  loss[1] += loss[0]     (skipped when loss == NULL; scale = 1 / N is torch's "mean")
+ *   counts[0] += rows whose top-1 (pleas_top1_count's rule) is their label;  counts[1] += rows with a label outside [0, C)
+ * A label outside [0, C) never indexes memory: its row has loss 0, a zero dlogits row and no hit (torch's ignore_index is NOT
+ * implemented: the caller reads counts[1] back with its other results and treats a non-zero value as an error).
+ * logits / dlogits [N][C] contiguous fp32, labels DEVICE int64[N], row_loss DEVICE fp32[N] (scratch the caller owns),
+ * loss DEVICE fp32[2], counts DEVICE int64[2] (8-byte aligned; the caller zeroes them once and reads them once per loop).
+ * -inf logits are legal (probability 0; at the label: +inf loss).  Every floating-point sum has a fixed order (the sum over
+ * rows is a second, one-workgroup grid; loss[1] is updated by one thread) and the counters are integer atomics, one per
+ * workgroup: the same call gives the same bits.  16-byte accesses when C % 4 == 0 and logits / dlogits are 16-byte aligned.
+ * N == 0: nothing is enqueued, returns 0.  C < 1, N * C >= 2^30 or dlogits == logits: PLEAS_EINVAL. */
+int pleas_softmax_xent(const float* logits, const int64_t* labels, int64_t N, int C, float scale, float* dlogits,
+                       float* row_loss, float* loss, int64_t* counts, void* stream);
+
 /* Train-mode BatchNorm of the matching forward, folded to the same per-channel affine map.
  *
  * Replaces: the BatchNorm2d modules inside the cross module's forward when the caller's models are in train mode --

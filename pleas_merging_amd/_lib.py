@@ -80,6 +80,7 @@ SIGNATURES = {
     "pleas_conv2d_act_fwd": (c_int, [c_void_p] * 7 + [c_int] * 11 + [c_void_p]),
     "pleas_pool_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p]),
     "pleas_top1_count": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "pleas_softmax_xent": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pleas_wgrad_batch_ws_bytes": (c_size_t, [c_void_p, c_int]),
     "pleas_wgrad_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "pleas_wgrad_plan_info": (c_int, [c_void_p, c_int, POINTER(c_int)]),

@@ -342,6 +342,217 @@ __global__ __launch_bounds__(kEwThreads) void top1_count_kernel(const float* __r
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Softmax cross-entropy of logits[N][C] against labels[N] from ONE pass over HBM: per row the loss, the gradient of the (scaled)
+// summed loss with respect to the logits, and whether the row's top-1 (top1_count_kernel's rule) is its label.
+//   m = max_c x_c;  s = sum_c exp(x_c - m);  row_loss = log(s) + (m - x_label)   (torch's log_softmax + nll_loss, term by term)
+//   dlogits[c] = scale * (exp(x_c - m) / s - [c == label])
+// A label outside [0, C) indexes nothing: loss 0, a zero gradient row, no hit, one more bad label.
+// Two forms.  WAVE (C <= kXentWaveCols): a wave per row, the row in registers (lane l holds the 16-byte pieces -- or, for rows
+// that are not 16-byte aligned, the single columns -- l, l + 64, ...), reductions by xor trees over the lanes.  BLOCK: a
+// workgroup per row and three sweeps (maximum, sum, gradient); the second and third come from L2.  Either way every sum has a
+// fixed order: the same bits run after run.  Hits and bad labels leave a workgroup as one 64-bit integer atomic each.
+constexpr int kXentWaveCols = 1024;     // 16 values per lane
+
+__device__ __forceinline__ void xent_scan(float v, int i, float& bv, int& bi) {
+    if (top1_better(v, i, bv, bi)) { bv = v; bi = i; }
+}
+__device__ __forceinline__ void xent_wave_top1(float& bv, int& bi) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        if (top1_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+}
+__device__ __forceinline__ float xent_wave_sum(float s) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+// a workgroup's hit / bad-label counts (kept by lane 0 of every wave) -> the two device counters
+__device__ __forceinline__ void xent_counts_out(int hit, int bad, unsigned long long* counts) {
+    __shared__ int wave_counts[2][kEwThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { wave_counts[0][wave] = hit; wave_counts[1][wave] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0 && counts) {
+        int h = 0, b = 0;
+        for (int w = 0; w < kEwThreads / 64; ++w) { h += wave_counts[0][w]; b += wave_counts[1][w]; }
+        if (h) atomicAdd(counts, (unsigned long long)h);
+        if (b) atomicAdd(counts + 1, (unsigned long long)b);
+    }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kEwThreads) void softmax_xent_wave_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                       int64_t N, int C, float scale, float* __restrict__ dlogits,
+                                                                       float* __restrict__ row_loss, unsigned long long* __restrict__ counts) {
+    constexpr int kPieces = kXentWaveCols / 64 / VEC;      // pieces of VEC columns per lane
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pieces = (C + VEC - 1) / VEC;                // VEC == 4: C % 4 == 0
+    int hit = 0, bad = 0;
+    for (int64_t row = (int64_t)blockIdx.x * (kEwThreads / 64) + wave; row < N; row += (int64_t)gridDim.x * (kEwThreads / 64)) {
+        const float* in = logits + row * C;
+        const int64_t label = labels[row];
+        const bool legal = label >= 0 && label < (int64_t)C;
+        float x[kPieces * VEC];
+        float bv = -__builtin_inff();
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < kPieces; ++j) {
+            const int q = lane + 64 * j;
+            if (q < pieces) {
+                if constexpr (VEC == 4) {
+                    const f32x4 v = reinterpret_cast<const f32x4*>(in)[q];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x[4 * j + e] = v[e];
+                } else {
+                    x[j] = in[q];
+                }
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) xent_scan(x[VEC * j + e], VEC * q + e, bv, bi);
+            }
+        }
+        xent_wave_top1(bv, bi);
+        const float m = bv;
+        float s = 0.f, xl = 0.f;                           // xl: the label's logit (held by one lane, summed over the wave)
+#pragma unroll
+        for (int j = 0; j < kPieces; ++j) {
+            const int q = lane + 64 * j;
+            if (q < pieces) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const float v = x[VEC * j + e];
+                    if (legal && (int64_t)(VEC * q + e) == label) xl = m - v;
+                    x[VEC * j + e] = expf(v - m);
+                    s += x[VEC * j + e];
+                }
+            }
+        }
+        s = xent_wave_sum(s);
+        xl = xent_wave_sum(xl);                            // one lane holds m - x_label, the others 0: exact
+        if (lane == 0) {
+            row_loss[row] = legal ? logf(s) + xl : 0.f;
+            hit += legal && label == (int64_t)bi ? 1 : 0;
+            bad += legal ? 0 : 1;
+        }
+        if (dlogits) {
+            float* out = dlogits + row * C;
+#pragma unroll
+            for (int j = 0; j < kPieces; ++j) {
+                const int q = lane + 64 * j;
+                if (q < pieces) {
+                    float d[VEC];
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e)
+                        d[e] = legal ? scale * (x[VEC * j + e] / s - ((int64_t)(VEC * q + e) == label ? 1.f : 0.f)) : 0.f;
+                    if constexpr (VEC == 4) reinterpret_cast<f32x4*>(out)[q] = f32x4{d[0], d[1], d[2], d[3]};
+                    else out[q] = d[0];
+                }
+            }
+        }
+    }
+    xent_counts_out(hit, bad, counts);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kEwThreads) void softmax_xent_block_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                        int64_t N, int C, float scale, float* __restrict__ dlogits,
+                                                                        float* __restrict__ row_loss, unsigned long long* __restrict__ counts) {
+    __shared__ float wave_v[kEwThreads / 64];
+    __shared__ int wave_i[kEwThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pieces = (C + VEC - 1) / VEC;
+    int hit = 0, bad = 0;
+    for (int64_t row = blockIdx.x; row < N; row += gridDim.x) {
+        const float* in = logits + row * C;
+        const int64_t label = labels[row];
+        const bool legal = label >= 0 && label < (int64_t)C;
+        // sweep 1: the first maximal column
+        float bv = -__builtin_inff();
+        int bi = 0x7fffffff;
+        for (int q = tid; q < pieces; q += kEwThreads) {
+            if constexpr (VEC == 4) {
+                const f32x4 v = reinterpret_cast<const f32x4*>(in)[q];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xent_scan(v[e], 4 * q + e, bv, bi);
+            } else {
+                xent_scan(in[q], q, bv, bi);
+            }
+        }
+        xent_wave_top1(bv, bi);
+        if (lane == 0) { wave_v[wave] = bv; wave_i[wave] = bi; }
+        __syncthreads();
+        bv = wave_v[0];
+        bi = wave_i[0];
+        for (int w = 1; w < kEwThreads / 64; ++w) xent_scan(wave_v[w], wave_i[w], bv, bi);
+        __syncthreads();                                   // wave_v is reused by the sum
+        const float m = bv;
+        // sweep 2: the sum of exponentials, per thread in column order, then a tree over the lanes and the waves in order
+        float s = 0.f;
+        for (int q = tid; q < pieces; q += kEwThreads) {
+            if constexpr (VEC == 4) {
+                const f32x4 v = reinterpret_cast<const f32x4*>(in)[q];
+                s += (expf(v[0] - m) + expf(v[1] - m)) + (expf(v[2] - m) + expf(v[3] - m));
+            } else {
+                s += expf(in[q] - m);
+            }
+        }
+        s = xent_wave_sum(s);
+        if (lane == 0) wave_v[wave] = s;
+        __syncthreads();
+        s = wave_v[0];
+        for (int w = 1; w < kEwThreads / 64; ++w) s += wave_v[w];
+        __syncthreads();                                   // wave_v is reused by the next row
+        if (tid == 0) {
+            float l = 0.f;
+            if (legal) l = logf(s) + (m - in[label]);      // the only read indexed by a label: behind its range check
+            row_loss[row] = l;
+            hit += legal && label == (int64_t)bi ? 1 : 0;
+            bad += legal ? 0 : 1;
+        }
+        // sweep 3: the gradient row
+        if (dlogits) {
+            float* out = dlogits + row * C;
+            for (int q = tid; q < pieces; q += kEwThreads) {
+                if constexpr (VEC == 4) {
+                    const f32x4 v = reinterpret_cast<const f32x4*>(in)[q];
+                    f32x4 d;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        d[e] = legal ? scale * (expf(v[e] - m) / s - ((int64_t)(4 * q + e) == label ? 1.f : 0.f)) : 0.f;
+                    reinterpret_cast<f32x4*>(out)[q] = d;
+                } else {
+                    out[q] = legal ? scale * (expf(in[q] - m) / s - ((int64_t)q == label ? 1.f : 0.f)) : 0.f;
+                }
+            }
+        }
+    }
+    xent_counts_out(hit, bad, counts);
+}
+
+// loss[0] = scale * (row_loss[0] + ... in a fixed order), loss[1] += loss[0]: one workgroup, thread t sums rows t, t + 256, ...
+// in turn, then a tree over the threads; ONE thread updates the running sum.
+__global__ __launch_bounds__(kEwThreads) void softmax_xent_loss_kernel(const float* __restrict__ row_loss, int64_t N, float scale,
+                                                                       float* __restrict__ loss) {
+    __shared__ float red[kEwThreads];
+    const int tid = threadIdx.x;
+    float s = 0.f;
+    for (int64_t n = tid; n < N; n += kEwThreads) s += row_loss[n];
+    red[tid] = s;
+    __syncthreads();
+    for (int off = kEwThreads / 2; off >= 1; off >>= 1) {
+        if (tid < off) red[tid] += red[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float l = scale * red[0];
+        loss[0] = l;
+        loss[1] += l;
+    }
+}
+
 }  // namespace pleas
 
 using namespace pleas;
@@ -654,5 +865,43 @@ extern "C" int pleas_top1_count(const float* logits, const int64_t* labels, int6
     hipLaunchKernelGGL(top1_count_kernel, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream_, logits, labels, N, C,
                        reinterpret_cast<unsigned long long*>(hits), pred);
     PLEAS_LAUNCH_CHECK("top1_count_kernel");
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_softmax_xent(const float* logits, const int64_t* labels, int64_t N, int C, float scale, float* dlogits,
+                                  float* row_loss, float* loss, int64_t* counts, void* stream_) {
+    if (N < 0) return bad_arg("softmax_xent: N < 0");
+    if (N == 0) return PLEAS_OK;
+    if (!logits || !labels || !row_loss) return bad_arg("softmax_xent: null pointer");
+    if (C < 1) return bad_arg("softmax_xent: empty rows");
+    if (N >= ((int64_t)1 << 30) || N * C >= ((int64_t)1 << 30)) return bad_arg("softmax_xent: N * C must stay below 2^30");
+    if (dlogits == logits) return bad_arg("softmax_xent: dlogits must not alias logits");
+    if (((uintptr_t)counts & 7) != 0) return bad_arg("softmax_xent: counts must be 8-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
+    const bool vec = C % 4 == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)dlogits & 15) == 0;
+    if (C <= kXentWaveCols) {
+        const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(N, kEwThreads / 64), kEwMaxBlocks);
+        if (vec)
+            hipLaunchKernelGGL((softmax_xent_wave_kernel<4>), dim3(grid), dim3(kEwThreads), 0, stream, logits, labels, N, C, scale,
+                               dlogits, row_loss, cnt);
+        else
+            hipLaunchKernelGGL((softmax_xent_wave_kernel<1>), dim3(grid), dim3(kEwThreads), 0, stream, logits, labels, N, C, scale,
+                               dlogits, row_loss, cnt);
+        PLEAS_LAUNCH_CHECK("softmax_xent_wave_kernel");
+    } else {
+        const unsigned grid = (unsigned)std::min<int64_t>(N, kEwMaxBlocks);
+        if (vec)
+            hipLaunchKernelGGL((softmax_xent_block_kernel<4>), dim3(grid), dim3(kEwThreads), 0, stream, logits, labels, N, C, scale,
+                               dlogits, row_loss, cnt);
+        else
+            hipLaunchKernelGGL((softmax_xent_block_kernel<1>), dim3(grid), dim3(kEwThreads), 0, stream, logits, labels, N, C, scale,
+                               dlogits, row_loss, cnt);
+        PLEAS_LAUNCH_CHECK("softmax_xent_block_kernel");
+    }
+    if (loss) {
+        hipLaunchKernelGGL(softmax_xent_loss_kernel, dim3(1), dim3(kEwThreads), 0, stream, (const float*)row_loss, N, scale, loss);
+        PLEAS_LAUNCH_CHECK("softmax_xent_loss_kernel");
+    }
     return PLEAS_OK;
 }

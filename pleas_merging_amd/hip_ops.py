@@ -966,6 +966,42 @@ def top1_count(logits: torch.Tensor, labels: torch.Tensor, hits: torch.Tensor, p
     return hits
 
 
+def softmax_xent(logits: torch.Tensor, labels: torch.Tensor, scale: Optional[float] = None, dlogits: Optional[torch.Tensor] = None,
+                 row_loss: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
+                 counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Softmax cross-entropy of ``logits`` [N, C] fp32 against ``labels`` int64 [N] from one pass, no synchronisation
+    (``pleas_softmax_xent``): ``row_loss[n] = logsumexp(logits[n]) - logits[n, labels[n]]`` (allocated when not given, returned);
+    ``dlogits`` (optional, [N, C]) ``= scale * (softmax(logits) - onehot(labels))``; ``loss`` (optional, fp32 [2]):
+    ``loss[0] = scale * row_loss.sum()`` in a fixed order and ``loss[1] += loss[0]``; ``counts`` (optional, int64 [2]):
+    ``counts[0] +=`` rows whose top-1 (``top1_count``'s rule) is their label, ``counts[1] +=`` rows whose label lies outside
+    ``[0, C)`` -- such a row has loss 0, a zero ``dlogits`` row and no hit, and the caller raises when it reads ``counts`` back.
+    ``scale`` defaults to ``1 / N`` (``F.cross_entropy``'s ``reduction="mean"``)."""
+    _need_gpu(logits)
+    if logits.dim() != 2 or not logits.is_contiguous() or logits.shape[1] < 1:
+        raise PleasHipError("softmax_xent: logits must be a contiguous [N, C] tensor with C >= 1")
+    N, C = logits.shape
+    if N * C >= 1 << 30:
+        raise PleasHipError("softmax_xent: N * C = %d is not below 2^30" % (N * C))
+    if row_loss is None:
+        row_loss = torch.empty(N, dtype=torch.float32, device=logits.device)
+    for name, t, dtype, shape in (("labels", labels, torch.int64, (N,)), ("dlogits", dlogits, torch.float32, (N, C)),
+                                  ("row_loss", row_loss, torch.float32, (N,)), ("loss", loss, torch.float32, (2,)),
+                                  ("counts", counts, torch.int64, (2,))):
+        if t is not None and (t.device != logits.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise PleasHipError("softmax_xent: %s must be a contiguous %s tensor of shape %s on the logits' device" % (name, dtype, shape))
+    outs = [t for t in (dlogits, row_loss, loss) if t is not None]
+    for i, t in enumerate(outs):            # outputs overlap neither the logits nor each other
+        for o in [logits] + outs[:i]:
+            if t.numel() and o.numel() and t.data_ptr() < o.data_ptr() + o.numel() * 4 and o.data_ptr() < t.data_ptr() + t.numel() * 4:
+                raise PleasHipError("softmax_xent: dlogits / row_loss / loss must not overlap the logits or each other")
+    if N:
+        check(_lib.lib().pleas_softmax_xent(logits.data_ptr(), labels.data_ptr(), N, C, 1.0 / N if scale is None else float(scale),
+                                            dlogits.data_ptr() if dlogits is not None else None, row_loss.data_ptr(),
+                                            loss.data_ptr() if loss is not None else None,
+                                            counts.data_ptr() if counts is not None else None, _stream()), "pleas_softmax_xent")
+    return row_loss
+
+
 class WgradBatch(_GroupedLaunch):
     """Weight gradients of all merged layers of one update in ONE grouped launch (``pleas_wgrad_batch``).
     ``add`` per layer (operands must stay unmodified until ``flush``), ``flush`` once per update."""

@@ -13,4 +13,5 @@ from .extras import reset_bn_stats, zip_ratios, save_matching, load_matching, lo
 from .budget import count_linear_flops, partial_merge_flops, qp_ratios
 from .evaluation import (get_fc_perm, permute_final_features, final_feature_map, eval_perm_model, eval_whole_model,
                          train_eval_linear_probe)
+from .linear_probe import HipProbeHead, cosine_lrs_eta_min
 from .source_forward import InferenceBackbone

@@ -10,6 +10,10 @@ the BatchNorm / add / ReLU chain in their epilogue, one ``pool_gather`` for pool
 own Linear) and counts with ``hip_ops.top1_count`` into one device counter read back once after the loop; host batches are
 copied on the current stream without blocking the host.  It needs the model on the GPU (``PleasHipError`` otherwise) and a forward that no
 hook has to observe bit-for-bit in the vendor's arithmetic; hooks on convolutions still receive their outputs.
+
+``train_eval_linear_probe`` also takes ``head="hip"`` (default ``"autograd"``): the probe's head trained on the library's kernels
+without a read-back per step (methods/linear_probe.py), and ``cache_features=True``: the frozen backbone run once instead of
+once per epoch.
 """
 from __future__ import annotations
 
@@ -21,9 +25,11 @@ from torch import nn
 from .. import hip_ops
 from ..core.utils import Axis, Permutation, PermutationSpec
 from .partial_matching import get_blocks
+from .linear_probe import HipProbeHead, cosine_lrs_eta_min
 from .source_forward import HipLinear, InferenceBackbone
 
 BACKBONES = ("modules", "hip")
+HEADS = ("autograd", "hip")
 
 
 def get_fc_perm(perm: Permutation, spec: PermutationSpec, costs, budget_ratios):
@@ -138,8 +144,24 @@ def eval_whole_model(model: nn.Module, dataloader: Iterable, num_classes: int, b
     return acc
 
 
+def _probe_batches(features, dataloader, device: torch.device, non_blocking: bool = False):
+    """``(features(x), y)`` per batch of ``dataloader`` on ``device``, the frozen backbone under ``no_grad``."""
+    for x, y in dataloader:
+        x, y = x.to(device, non_blocking=non_blocking), y.to(device, non_blocking=non_blocking)
+        with torch.no_grad():
+            feats = features(x)
+        yield feats, y
+
+
+def _recorded(batches, store: list):
+    for item in batches:
+        store.append(item)
+        yield item
+
+
 def train_eval_linear_probe(model: nn.Module, train_dataloader, test_dataloader, num_classes: int, wandb_run, dataset_name: str,
-                            lr: float = 1e-3, epochs: int = 10, device=None, backbone: str = "modules") -> nn.Module:
+                            lr: float = 1e-3, epochs: int = 10, device=None, backbone: str = "modules", head: str = "autograd",
+                            cache_features: bool = False) -> nn.Module:
     """Linear probe on a frozen (merged) backbone, as the different-label-space driver evaluates merged models
     (reference :499-570; run_torchvision.py:276-290).  Same recipe: Adam(``lr``) on a fresh ``Linear`` head, cosine
     schedule over ``epochs * len(train_dataloader)`` steps down to ``lr / 10``, cross entropy, backbone in eval mode
@@ -147,23 +169,48 @@ def train_eval_linear_probe(model: nn.Module, train_dataloader, test_dataloader,
     reference's keys (``wandb_run=None`` skips logging).  Returns the trained head.  The backbone stays where it is
     (``device`` defaults to its device) -- the reference hard-codes ``.cuda()`` and a 224x224 probe input; here the
     feature width is read from the first training batch.  ``backbone="hip"`` moves the frozen backbone's forwards to the
-    library's kernels; the head's Adam / cross entropy stay on autograd."""
+    library's kernels.
+
+    ``head="autograd"`` (default) trains the head as the reference does: ``nn.Linear``, ``CrossEntropyLoss``, ``torch.optim.Adam``
+    and ``CosineAnnealingLR`` on autograd, one ``float(loss)`` read-back per step.  ``head="hip"`` trains the same head by the
+    same recipe on the library's kernels (``linear_probe.HipProbeHead``: own Linear forward, ``softmax_xent``, one grouped weight
+    gradient, ``channel_sum``, one ``masked_adam``; the test accuracy by ``top1_count``): five launches per step, ONE read-back per
+    epoch and one for the test loop; batches are copied without blocking the host.  It needs the model on the GPU
+    (``PleasHipError`` otherwise, no CPU fallback), works with either ``backbone`` and returns an ``nn.Linear`` as well.
+
+    ``cache_features=True`` (either head) runs the backbone ONCE over the training loader, during epoch 0, and keeps every
+    feature and label batch on the device (``N_total * D * 4`` bytes); epochs 1, 2, ... replay epoch 0's batches in epoch 0's
+    order.  THIS CHANGES THE RECIPE: a loader that reshuffles or augments per epoch no longer does so after epoch 0, the head
+    sees the same batches in the same order every epoch.  It is therefore opt-in; with a deterministic, unshuffled loader the
+    result is the one of ``cache_features=False``."""
+    if head not in HEADS:
+        raise ValueError("head must be one of %r, got %r" % (HEADS, head))
     own_device, hip = _hip_backbone(model, backbone)
     if device is None:
         device = own_device
+    device = torch.device(device)
+    if head == "hip" and (own_device.type != "cuda" or device.type != "cuda"):
+        raise hip_ops.PleasHipError('head="hip" needs the model on the GPU (got %s); no CPU fallback' % own_device)
     model.eval()
     features = hip if hip is not None else model
     n_batches = len(train_dataloader)
+    log = wandb_run.log if wandb_run is not None else (lambda _metrics: None)
+    cached = [] if cache_features else None
+
+    def train_batches(epoch: int):
+        if cached is not None and epoch > 0:
+            return cached
+        batches = _probe_batches(features, train_dataloader, device, non_blocking=head == "hip")
+        return batches if cached is None else _recorded(batches, cached)
+
+    if head == "hip":
+        return _hip_probe(features, train_batches, test_dataloader, num_classes, log, dataset_name, lr, epochs, device, n_batches)
     fc = opt = sched = None
     loss_fn = nn.CrossEntropyLoss()
-    log = wandb_run.log if wandb_run is not None else (lambda _metrics: None)
     for epoch in range(epochs):
         hit = torch.zeros((), dtype=torch.long, device=device)
         seen, total, loss = 0, 0.0, None
-        for x, y in train_dataloader:
-            x, y = x.to(device), y.to(device)
-            with torch.no_grad():
-                feats = features(x)
+        for feats, y in train_batches(epoch):
             if fc is None:
                 fc = nn.Linear(feats.shape[-1], num_classes).to(device)
                 opt = torch.optim.Adam(fc.parameters(), lr=lr)
@@ -186,9 +233,40 @@ def train_eval_linear_probe(model: nn.Module, train_dataloader, test_dataloader,
     fc.eval()
     hit, seen = torch.zeros((), dtype=torch.long, device=device), 0
     with torch.no_grad():
-        for x, y in test_dataloader:
-            x, y = x.to(device), y.to(device)
-            hit += (fc(features(x)).argmax(1) == y).sum()
+        for feats, y in _probe_batches(features, test_dataloader, device):
+            hit += (fc(feats).argmax(1) == y).sum()
             seen += int(y.numel())
     log({"%s_linear_probe_acc" % dataset_name: float(hit) / max(seen, 1)})
     return fc
+
+
+def _hip_probe(features, train_batches, test_dataloader, num_classes: int, log, dataset_name: str, lr: float, epochs: int,
+               device: torch.device, n_batches: int) -> nn.Linear:
+    """``train_eval_linear_probe`` with ``head="hip"``: the same loop, every step enqueued without a read-back."""
+    lrs = cosine_lrs_eta_min(lr, lr / 10, max(epochs * n_batches, 1), epochs * n_batches)
+    probe, t = None, 0
+    for epoch in range(epochs):
+        seen = 0
+        for feats, y in train_batches(epoch):
+            if probe is None:
+                probe = HipProbeHead(nn.Linear(feats.shape[-1], num_classes).to(device))
+            if t >= len(lrs):
+                raise ValueError("train_eval_linear_probe: the training loader yields more batches than its len() = %d" % n_batches)
+            probe.step(feats, _labels(y), lrs[t], t + 1)
+            t += 1
+            seen += int(y.numel())
+        if probe is None:
+            break
+        hits, _bad, total, last = probe.epoch_readback()      # the epoch's one read-back
+        log({"%s_linear_probe_train_acc" % dataset_name: hits / max(seen, 1),
+             "%s_linear_probe_train_loss" % dataset_name: last if seen else float("nan"),
+             "epoch": epoch, "%s_total_loss" % dataset_name: total / max(n_batches, 1)})
+    if probe is None:
+        raise ValueError("train_eval_linear_probe: empty training loader")
+    seen = 0
+    for feats, y in _probe_batches(features, test_dataloader, device, non_blocking=True):
+        hip_ops.top1_count(probe.logits(feats), _labels(y), probe.counts[:1])
+        seen += int(y.numel())
+    hits = probe.epoch_readback()[0]                          # the test loop's one read-back
+    log({"%s_linear_probe_acc" % dataset_name: hits / max(seen, 1)})
+    return probe.finish()
