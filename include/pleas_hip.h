@@ -406,6 +406,27 @@ int pleas_conv2d_bn_act_fwd(const float* x, const float* w, const float* bias, f
 int pleas_conv2d_act_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
                          const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH, int KW,
                          int stride, int pad, int flags, void* stream);
+/* pleas_conv2d_bn_stats_fwd: the convolution of pleas_conv2d_fwd followed by a TRAIN-mode BatchNorm2d's fold, with the batch
+ * statistics taken in the convolution's epilogue instead of from a second pass over y:
+ *   y = conv(x, w) (+ bias)                            stored, bit for bit what pleas_conv2d_fwd stores
+ *   scale, shift [batches][Cout], running statistics and counter: as pleas_bn_train_fold_batches on y would leave them
+ * Replaces: Conv2d -> BatchNorm2d(training) of the BN-statistics reset that every driver runs on the merged model
+ *   (experiments/shared_label_space/run_domainnet.py:327-341): the vendor convolution (its 3 x 3 kernels split K with atomics:
+ *   not repeatable) and the statistics pass over its output.
+ * Three kernels on `stream`: the convolution, whose work items leave fp64 sums of y and y^2 per channel over their tile's pixels
+ * (y = the stored fp32 value; two segments per tile, for the batch of its first pixel and for the next one); a reduce over the
+ * tiles per (batch, channel); the finalize kernel of pleas_bn_train_fold_batches.  Fixed orders, no atomics.
+ *   N: ALL samples, N % batches == 0, batch b = samples b * N / batches ..; geometry limits, flags and pleas_arith modes as
+ *   pleas_conv2d_fwd; gamma / beta / eps / momentum / running_* / num_batches_tracked as pleas_bn_train_fold_batches.
+ * Refused with PLEAS_EINVAL before anything is enqueued: NULL x / w / y / scale / shift, batches < 1, N % batches != 0, one value
+ *   per channel and batch, one running pointer without the other, a misaligned ws, and batches > 1 with fewer than 128 output
+ *   pixels per batch (a tile would touch more than two batches: fold those after pleas_conv2d_fwd).  PLEAS_ENOMEM: ws NULL or
+ *   smaller than pleas_conv2d_bn_stats_ws_bytes(N, Cout, Hout, Wout, batches) (8-byte aligned, caller-owned; 0 for empty shapes). */
+size_t pleas_conv2d_bn_stats_ws_bytes(int N, int Cout, int Hout, int Wout, int batches);
+int pleas_conv2d_bn_stats_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Hin, int Win,
+                              int Cout, int KH, int KW, int stride, int pad, int flags, int batches, const float* gamma,
+                              const float* beta, double eps, double momentum, float* running_mean, float* running_var,
+                              int64_t* num_batches_tracked, float* scale, float* shift, void* ws, size_t ws_bytes, void* stream);
 typedef struct pleas_wgrad_layer {
     const float* resid; /* [N][Cout][Hout*Wout] */
     const float* ip;    /* [N][Cin][Hin][Win]   */

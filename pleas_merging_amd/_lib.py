@@ -78,6 +78,9 @@ SIGNATURES = {
     "pleas_conv2d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p]),
     "pleas_conv2d_bn_act_fwd": (c_int, [c_void_p] * 8 + [c_int] * 11 + [c_void_p]),
     "pleas_conv2d_act_fwd": (c_int, [c_void_p] * 7 + [c_int] * 11 + [c_void_p]),
+    "pleas_conv2d_bn_stats_ws_bytes": (c_size_t, [c_int] * 5),
+    "pleas_conv2d_bn_stats_fwd": (c_int, [c_void_p] * 4 + [c_int] * 11 + [c_void_p, c_void_p, ctypes.c_double, ctypes.c_double]
+                                  + [c_void_p] * 6 + [c_size_t, c_void_p]),
     "pleas_pool_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p]),
     "pleas_top1_count": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "pleas_softmax_xent": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

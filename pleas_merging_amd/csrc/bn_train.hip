@@ -10,6 +10,7 @@
 //
 //   bn_stats_partial_kernel   grid (C, S): workgroup (c, s) sums x and x^2 of channel c over samples n = s, s+S, ...
 //                             (every (n, c) slab is HW contiguous floats: 16-B loads), fp64 accumulation
+//   bn_tile_reduce_kernel     the same sums from the partials a convolution left per tile (pleas_conv2d_bn_stats_fwd): y is not read
 //   bn_train_finalize_kernel  one workgroup: per channel combines the S partials in a fixed order (deterministic), writes
 //                             scale / shift, updates running_mean / running_var (unbiased) with the momentum or the
 //                             cumulative average, then bumps num_batches_tracked
@@ -123,6 +124,57 @@ __global__ __launch_bounds__(1024) void bn_train_finalize_kernel(double* __restr
         }
     }
     if (threadIdx.x == 0 && num_batches_tracked) *num_batches_tracked += batches;
+}
+
+// The tiles' partial sums of a convolution that emitted them (conv_fwd.hip, PLAIN == 4) -> one sum per (batch, channel).
+// Workgroup (channel block, batch): kRedCh channels x kRedRuns runs of consecutive tiles; a thread adds its run's tiles in tile
+// order, thread (channel, 0) then adds the runs in run order -- fixed, no atomics.  Lanes of neighbouring channels read neighbouring
+// 16 bytes.  Many workgroups: ResNet-101's merged layer1 at 64 samples leaves 1568 tiles x 384 channels = 19 MB of partials.
+constexpr int kRedCh = 16, kRedRuns = 16;
+__global__ __launch_bounds__(kRedCh * kRedRuns) void bn_tile_reduce_kernel(const double* __restrict__ tile_part, int tile, uint32_t ptot,
+                                                                           uint32_t per_batch, int channels, double* __restrict__ sums) {
+    const int bt = blockIdx.y;
+    const int lc = threadIdx.x % kRedCh, run = threadIdx.x / kRedCh;
+    const int c = blockIdx.x * kRedCh + lc;
+    // the batch's pixels [first, last] and the tiles that hold them
+    const uint32_t first = (uint32_t)bt * per_batch, last = min(first + per_batch, ptot) - 1u;
+    const uint32_t t_lo = first / (uint32_t)tile, t_hi = last / (uint32_t)tile;
+    const uint32_t per_run = (t_hi - t_lo + kRedRuns) / kRedRuns;
+    const uint32_t t0 = t_lo + (uint32_t)run * per_run, t1 = min(t0 + per_run, t_hi + 1u);
+    double a = 0.0, b = 0.0;
+    if (c < channels)
+        for (uint32_t t = t0; t < t1; ++t) {
+            // segment 0 belongs to the batch of the tile's first pixel, segment 1 to the next one
+            const uint32_t seg = (uint32_t)bt - (t * (uint32_t)tile) / per_batch;
+            const double* p = tile_part + (((int64_t)t * 2 + seg) * channels + c) * 2;
+            a += p[0];
+            b += p[1];
+        }
+    __shared__ double sa[kRedRuns][kRedCh], sb[kRedRuns][kRedCh];
+    sa[run][lc] = a;
+    sb[run][lc] = b;
+    __syncthreads();
+    if (run == 0 && c < channels) {
+        double ta = 0.0, tb = 0.0;
+        for (int r = 0; r < kRedRuns; ++r) {
+            ta += sa[r][lc];
+            tb += sb[r][lc];
+        }
+        sums[((int64_t)bt * channels + c) * 2 + 0] = ta;
+        sums[((int64_t)bt * channels + c) * 2 + 1] = tb;
+    }
+}
+
+int bn_fold_tile_partials(const double* tile_part, int tile, uint32_t ptot, uint32_t per_batch, int channels, int batches, double* sums,
+                          const float* gamma, const float* beta, double eps, double momentum, float* running_mean, float* running_var,
+                          int64_t* num_batches_tracked, float* scale, float* shift, hipStream_t stream) {
+    hipLaunchKernelGGL(bn_tile_reduce_kernel, dim3((unsigned)ceil_div(channels, kRedCh), (unsigned)batches), dim3(kRedCh * kRedRuns), 0,
+                       stream, tile_part, tile, ptot, per_batch, channels, sums);
+    PLEAS_LAUNCH_CHECK("bn_tile_reduce_kernel");
+    hipLaunchKernelGGL(bn_train_finalize_kernel, dim3(1), dim3(1024), 0, stream, sums, 1, channels, batches, (double)per_batch, gamma,
+                       beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale, shift);
+    PLEAS_LAUNCH_CHECK("bn_train_finalize_kernel");
+    return PLEAS_OK;
 }
 
 static inline int bn_splits(int64_t n, int channels) {

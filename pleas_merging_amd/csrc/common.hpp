@@ -117,6 +117,14 @@ constexpr int split_products(int split) { return split == 2 ? 9 : 6; }
 // a kernel has the form
 int arith_mode();
 
+// bn_train.hip, for the convolution that emits its output's batch statistics (conv_fwd.hip): `tile_part` [pixel tiles][2][channels][2]
+// holds, per tile of `tile` pixels (of ptot, `per_batch` to a batch) and channel, the sums of y and y^2 over the tile's pixels of
+// the first batch it touches (segment 0) and of the next one (segment 1).  Sums them per (batch, channel) into `sums`
+// [batches][channels][2] (+ a moments tail of the same size) and folds them with bn_train_finalize_kernel (S = 1).
+int bn_fold_tile_partials(const double* tile_part, int tile, uint32_t ptot, uint32_t per_batch, int channels, int batches, double* sums,
+                          const float* gamma, const float* beta, double eps, double momentum, float* running_mean, float* running_var,
+                          int64_t* num_batches_tracked, float* scale, float* shift, hipStream_t stream);
+
 
 // ---- opt-in per-kernel timing with HIP events on the launch stream (pleas_prof_* in the C-ABI)
 enum ProfKernel { kProfGramPartial = 0, kProfGramFinalize, kProfLsap, kProfMergeBlocks, kProfMaskedAdam, kProfSqerr,

@@ -53,7 +53,7 @@ struct FwdLayerDev {
     int variant;          // bit0: TM == 64, bit1: scalar W loads, bit2: W is kernel-position-major [Cout][KH*KW][Cin],
                           // bit3: flat-shift tile (fwd_flat_tile), bits 4-5: its KIND
     int part_base;        // first loss-partial slot of this layer
-    int bn_relu;          // PLAIN >= 2: ReLU after the affine map (+ identity)
+    int bn_relu;          // PLAIN 2 / 3: ReLU after the affine map (+ identity)
     // PLAIN == 2 (pleas_conv2d_bn_act_fwd): the convolution's output goes to `resid` AND its activated image
     // z = act(y * bn_scale[co] + bn_shift[co] (+ bn_res)) to `bn_z` -- the BatchNorm / add / ReLU pass that follows a frozen
     // source's convolution, without reading y back from memory
@@ -62,6 +62,11 @@ struct FwdLayerDev {
     const float* bn_res;     // [N][Cout][HWo] or null
     float* bn_z;             // [N][Cout][HWo]
     // PLAIN == 3 (pleas_conv2d_act_fwd): the same arithmetic, the activated image ALONE is stored (`resid` is null and unused)
+    // PLAIN == 4 (pleas_conv2d_bn_stats_fwd): the output goes to `resid` as under PLAIN == 1, and every work item leaves the sums
+    // of y and y^2 over its tile's live pixels, per output channel, in `st_part` [pixel tile][2][Cout][2] doubles: segment 0 for
+    // the batch the tile's first pixel belongs to, segment 1 for the next one (`st_pb` pixels per batch, >= fTN or all of them)
+    double* st_part;
+    uint32_t st_pb;
 };
 struct FwdItemDev {
     int layer, tm, tp, slot;  // slot: loss-partial index
@@ -83,13 +88,15 @@ struct FwdRowOps<TM, 2> {
 };
 template <int TM>
 struct FwdRowOps<TM, 3> : FwdRowOps<TM, 2> {};
+// the modes whose epilogue applies the BatchNorm map (the others take the primary template's block maps)
+constexpr bool fwd_has_image(int plain) { return plain == 2 || plain == 3; }
 template <int TM, int PLAIN = 0>
 __device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0, FwdRowOps<TM, PLAIN>& ops) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int j = 0; j < TM / 8; ++j) {
         const int co = min(i0 + (tid >> 5) + 8 * j, L.Cout - 1);
-        if constexpr (PLAIN >= 2) {
+        if constexpr (fwd_has_image(PLAIN)) {
             ops.scale[j] = PLEAS_GLOBAL(L.bn_scale)[co];
             ops.shift[j] = PLEAS_GLOBAL(L.bn_shift)[co];
         } else {
@@ -107,6 +114,9 @@ __device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0
 // the gather slots of the target
 // PLAIN = 3 (pleas_conv2d_act_fwd): PLAIN = 2 without the store of y -- a compile-time mode, so that the kernels of the other
 // modes stay the code they were
+// PLAIN = 4 (pleas_conv2d_bn_stats_fwd): PLAIN = 1, then a statistics pass over the tile while it is still in LDS: per output
+// channel the sums of y and y^2 (fp64, y = the fp32 value that was stored) over the tile's live pixels, split at a batch
+// boundary, in a fixed order and without atomics -- what bn_stats_partial_kernel (bn_train.hip) would read y back for
 template <int TM, int PLAIN = 0>
 __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItemDev& it, f32x16 (&acc)[TM / 64][2],
                                              const FwdRowOps<TM, PLAIN>& ops, float* smem, float* __restrict__ partials) {
@@ -133,6 +143,10 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
         __syncthreads();
     };
     float sq = 0.f;
+    // PLAIN == 4: the statistics pass gives TM / 256 threads to a channel row; that row's bias is requested here, ahead of the spill
+    constexpr int SPR = kThreads / TM;       // threads per row of the statistics pass
+    float st_bias = 0.f;
+    if constexpr (PLAIN == 4) st_bias = L.bias ? PLEAS_GLOBAL(L.bias)[min(i0 + tid / SPR, L.Cout - 1)] : 0.f;
     const bool vec_ok = (L.HWo % 4 == 0);   // then a 4-pixel group never straddles samples and is 16-B aligned
     const int pg = (tid & 31) * 4;           // pixel group of this thread
     const uint32_t Pg = p0 + pg;
@@ -151,8 +165,8 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
         const uint32_t gbase = 4u * (gn * (uint32_t)L.Csrc * L.HWo + gp);
         const uint32_t rbase = 4u * ((gn * (uint32_t)L.Cout + (uint32_t)i0 + (uint32_t)(tid >> 5)) * L.HWo + gp);
         // PLAIN == 2: the identity (shaped like the output) stands where the first source's outputs are gathered from
-        const bool has_res = PLAIN >= 2 && L.bn_res != nullptr;
-        const char* o1b = reinterpret_cast<const char*>(PLAIN >= 2 ? (has_res ? L.bn_res : L.ip) : L.o1);
+        const bool has_res = fwd_has_image(PLAIN) && L.bn_res != nullptr;
+        const char* o1b = reinterpret_cast<const char*>(fwd_has_image(PLAIN) ? (has_res ? L.bn_res : L.ip) : L.o1);
         const char* o2b = reinterpret_cast<const char*>(L.o2);
         char* rb_ = reinterpret_cast<char*>(L.resid);
         char* zb_ = reinterpret_cast<char*>(L.bn_z);
@@ -160,7 +174,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
 #pragma unroll
             for (int u = 0; u < GB; ++u) {
                 const int j = bt * GB + u;
-                if constexpr (PLAIN >= 2) {
+                if constexpr (fwd_has_image(PLAIN)) {
                     // unconditional load from a valid address (the output's own offset into the identity; the first floats
                     // of the input for rows / pixels outside the layer and when there is no identity -- then voided by a
                     // select): no branch around a load
@@ -184,7 +198,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const int j = bt * GB + u;
                 const int lco = (tid >> 5) + 8 * j, co = i0 + lco;
                 const bool live = gin && co < L.Cout;
-                if constexpr (PLAIN >= 2) {
+                if constexpr (fwd_has_image(PLAIN)) {
                     const f32x4 o = *reinterpret_cast<const f32x4*>(Ct + lco * EL + pg);
                     f32x4 y, z;
 #pragma unroll
@@ -234,7 +248,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const uint32_t Pe = Pg + e;
                 if (Pe >= L.Ptot) break;
                 const uint32_t n = Pe / L.HWo, p = Pe - n * L.HWo;
-                if constexpr (PLAIN >= 2) {
+                if constexpr (fwd_has_image(PLAIN)) {
                     const size_t at = ((size_t)n * L.Cout + co) * L.HWo + p;
                     const float y = o[e] + ops.bias[j];
                     const float sm = fmaf(y, ops.scale[j], ops.shift[j]) + (L.bn_res ? PLEAS_GLOBAL(L.bn_res)[at] : 0.f);
@@ -248,6 +262,65 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                     sq = fmaf(dd, dd, sq);
                     PLEAS_GLOBAL_W(L.resid)[((size_t)n * L.Cout + co) * L.HWo + p] = L.dscale * dd;
                 }
+            }
+        }
+    }
+    if constexpr (PLAIN == 4) {
+        // Thread (row r, part q) sums NCH 16-byte groups of its row: q's groups are q * NCH .. + NCH - 1, visited from a start
+        // that is rotated per q so that the 16 lanes of a ds_read_b128 group fall on 16 different bank quads (rows are 33 quads
+        // apart).  The order is a function of (r, q) alone: the same bits run after run.
+        constexpr int NCH = 32 / SPR;
+        const int r = tid / SPR, q = tid % SPR;
+        const int skew = (NCH / 2) * (SPR == 2 ? q : q >> 1);
+        // live pixels of the tile: [0, n0) belong to the first batch it touches, [n0, n1) to the next one
+        const uint32_t bnext = (p0 / L.st_pb + 1u) * L.st_pb;
+        const uint32_t n1 = min(L.Ptot - p0, (uint32_t)fTN), n0 = min(bnext - p0, n1);
+        double a0 = 0.0, b0 = 0.0, a1 = 0.0, b1 = 0.0;
+        const float* row = Ct + r * EL + q * NCH * 4;
+        if (n0 == (uint32_t)fTN) {           // block-uniform: a whole tile inside one batch, nothing to select
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const f32x4 o = *reinterpret_cast<const f32x4*>(row + 4 * ((i + skew) % NCH));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const double v = (double)(o[e] + st_bias);
+                    a0 += v;
+                    b0 = fma(v, v, b0);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const int g = (i + skew) % NCH;
+                const f32x4 o = *reinterpret_cast<const f32x4*>(row + 4 * g);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t px = (uint32_t)(4 * (q * NCH + g) + e);
+                    const double v = (double)(o[e] + st_bias);
+                    const double v0 = px < n0 ? v : 0.0, v1 = (px >= n0 && px < n1) ? v : 0.0;
+                    a0 += v0;
+                    b0 = fma(v0, v0, b0);
+                    a1 += v1;
+                    b1 = fma(v1, v1, b1);
+                }
+            }
+        }
+        // the row's SPR parts: a butterfly over adjacent lanes (every lane ends with the same sum, formed in the same order)
+#pragma unroll
+        for (int off = 1; off < SPR; off <<= 1) {
+            a0 += __shfl_xor(a0, off);
+            b0 += __shfl_xor(b0, off);
+            a1 += __shfl_xor(a1, off);
+            b1 += __shfl_xor(b1, off);
+        }
+        const int co = i0 + r;
+        if (q == 0 && co < L.Cout) {
+            double* seg = L.st_part + ((size_t)it.tp * 2 * L.Cout + co) * 2;
+            seg[0] = a0;
+            seg[1] = b0;
+            if (n1 > n0) {                   // block-uniform: the tile reaches into the next batch
+                seg[(size_t)L.Cout * 2 + 0] = a1;
+                seg[(size_t)L.Cout * 2 + 1] = b1;
             }
         }
     }
@@ -886,14 +959,15 @@ __global__ __launch_bounds__(kThreads, kFwdForms[FORM].occupancy[SPLIT]) void co
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const FwdItemDev it{0, (int)(blockIdx.x % (unsigned)tms), (int)(blockIdx.x / (unsigned)tms), 0};
     constexpr FwdForm F = kFwdForms[FORM];
-    constexpr int PLAIN = 1 + BN;      // 2: the BatchNorm / add / ReLU image is written beside the output; 3: that image alone
+    constexpr int PLAIN = 1 + BN;      // 2: the BatchNorm / add / ReLU image is written beside the output; 3: that image alone;
+                                       // 4: the output and its tile's batch statistics
     if constexpr (F.flat) fwd_flat_tile<F.tm, F.sub, SPLIT, PLAIN>(L, it, smem, nullptr);
     else fwd_tile<F.tm, F.sub, PLAIN>(L, it, smem, nullptr);
 }
 // The kernels of a form, [arithmetic = pleas_arith's mode]: a form without split kernels keeps its exact one there.
 struct FwdFormKernels {
     void (*batch[3])(const FwdLayerDev*, const FwdItemDev*, float*);
-    void (*conv2d[3][3])(const FwdLayerDev, const int);      // [BN][arithmetic]; BN 2: image only
+    void (*conv2d[4][3])(const FwdLayerDev, const int);      // [BN][arithmetic]; BN 2: image only; BN 3: output + batch statistics
 };
 template <int FORM>
 static constexpr FwdFormKernels fwd_form_kernels() {
@@ -901,7 +975,8 @@ static constexpr FwdFormKernels fwd_form_kernels() {
     return {{fwd_batch_kernel<FORM, 0>, fwd_batch_kernel<FORM, S>, fwd_batch_kernel<FORM, S9>},
             {{conv2d_fwd_kernel<FORM, 0, 0>, conv2d_fwd_kernel<FORM, S, 0>, conv2d_fwd_kernel<FORM, S9, 0>},
              {conv2d_fwd_kernel<FORM, 0, 1>, conv2d_fwd_kernel<FORM, S, 1>, conv2d_fwd_kernel<FORM, S9, 1>},
-             {conv2d_fwd_kernel<FORM, 0, 2>, conv2d_fwd_kernel<FORM, S, 2>, conv2d_fwd_kernel<FORM, S9, 2>}}};
+             {conv2d_fwd_kernel<FORM, 0, 2>, conv2d_fwd_kernel<FORM, S, 2>, conv2d_fwd_kernel<FORM, S9, 2>},
+             {conv2d_fwd_kernel<FORM, 0, 3>, conv2d_fwd_kernel<FORM, S, 3>, conv2d_fwd_kernel<FORM, S9, 3>}}};
 }
 static const FwdFormKernels kFwdKernels[fForms] = {fwd_form_kernels<0>(), fwd_form_kernels<1>(), fwd_form_kernels<2>(), fwd_form_kernels<3>(),
                                                    fwd_form_kernels<4>(), fwd_form_kernels<5>(), fwd_form_kernels<6>(), fwd_form_kernels<7>(),
@@ -1169,10 +1244,12 @@ extern "C" size_t pleas_fwd_batch_ws_bytes(const pleas_fwd_layer* layers, int n_
 }
 
 // y = conv(x, w) (+ bias); with `scale`: also z = act(y * scale[c] + shift[c] (+ res)) in the same epilogue; `image_only`
-// (with `scale`): z alone, y is neither given nor stored
+// (with `scale`): z alone, y is neither given nor stored; `st_part` (without `scale`): the tiles' batch statistics beside y, st_pb
+// pixels per batch
 static int conv2d_launch(const float* x, const float* w, const float* bias, float* y, const float* scale, const float* shift,
                          const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH, int KW,
-                         int stride, int pad, int flags, void* stream_, bool image_only = false) {
+                         int stride, int pad, int flags, void* stream_, bool image_only = false, double* st_part = nullptr,
+                         uint32_t st_pb = 0) {
     if (!x || !w || (!y && !image_only)) return bad_arg("conv2d_fwd: null pointer");
     if (((uintptr_t)w & 15) != 0 || ((uintptr_t)x & 15) != 0) return bad_arg("conv2d_fwd: x and w must be 16-byte aligned");
     const bool bn = scale != nullptr;
@@ -1192,13 +1269,14 @@ static int conv2d_launch(const float* x, const float* w, const float* bias, floa
     d.ip = x; d.w = w; d.bias = bias; d.o1 = x; d.o2 = x; d.row1 = nullptr; d.row2 = nullptr; d.resid = y;
     d.part_base = 0;
     d.bn_scale = scale; d.bn_shift = shift; d.bn_res = res; d.bn_z = z; d.bn_relu = relu ? 1 : 0;
+    d.st_part = st_part; d.st_pb = st_pb;
     const int tms = (int)ceil_div(Cout, TM), tps = (int)ceil_div((int64_t)d.Ptot, fTN);
     const dim3 grid((unsigned)((int64_t)tms * tps));
     hipStream_t st = (hipStream_t)stream_;
     const double out_floats = (double)Cout * d.Ptot;
     ProfScope prof(kProfConv2d, 2.0 * Cout * (double)d.Kd * (double)d.Ptot,
                    ((double)Cin * N * Hin * Win + out_floats * ((bn && !image_only ? 2.0 : 1.0) + (res ? 1.0 : 0.0))) * sizeof(float), st);
-    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? (image_only ? 2 : 1) : 0][arith_mode()], grid, dim3(kThreads), lds, st,
+    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? (image_only ? 2 : 1) : (st_part ? 3 : 0)][arith_mode()], grid, dim3(kThreads), lds, st,
                        d, tms);
     PLEAS_LAUNCH_CHECK("conv2d_fwd_kernel");
     return PLEAS_OK;
@@ -1223,6 +1301,53 @@ extern "C" int pleas_conv2d_act_fwd(const float* x, const float* w, const float*
     if (!scale || !shift || !z) return bad_arg("conv2d_act_fwd: null pointer");
     return conv2d_launch(x, w, bias, nullptr, scale, shift, res, z, relu, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_,
                          true);
+}
+
+// Workspace of pleas_conv2d_bn_stats_fwd, in doubles: what bn_train_finalize_kernel takes with S = 1 -- the sums per (batch,
+// channel) [batches][1][Cout][2] and its moments tail [batches][Cout][2] -- then the tiles' partial slab [pixel tiles][2][Cout][2].
+static size_t conv_bn_stats_head(int Cout, int batches) { return (size_t)batches * Cout * 4; }
+
+extern "C" size_t pleas_conv2d_bn_stats_ws_bytes(int N, int Cout, int Hout, int Wout, int batches) {
+    if (N <= 0 || Cout <= 0 || Hout <= 0 || Wout <= 0 || batches <= 0) return 0;
+    const int64_t tiles = ceil_div((int64_t)N * Hout * Wout, fTN);
+    return (conv_bn_stats_head(Cout, batches) + (size_t)tiles * 2 * Cout * 2) * sizeof(double);
+}
+
+extern "C" int pleas_conv2d_bn_stats_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Hin, int Win,
+                                         int Cout, int KH, int KW, int stride, int pad, int flags, int batches, const float* gamma,
+                                         const float* beta, double eps, double momentum, float* running_mean, float* running_var,
+                                         int64_t* num_batches_tracked, float* scale, float* shift, void* ws, size_t ws_bytes,
+                                         void* stream_) {
+    // every refusal comes before the first HIP call: nothing is enqueued for a call that is turned down
+    if (!x || !w || !y || !scale || !shift) return bad_arg("conv2d_bn_stats_fwd: null pointer");
+    if (batches < 1 || batches > 65535) return bad_arg("conv2d_bn_stats_fwd: batches");
+    if (N <= 0 || N % batches != 0) return bad_arg("conv2d_bn_stats_fwd: the samples do not split into the batches");
+    if ((running_mean == nullptr) != (running_var == nullptr))
+        return bad_arg("conv2d_bn_stats_fwd: running_mean / running_var: both or neither");
+    pleas_fwd_layer l{};
+    l.N = N; l.Cout = Cout; l.Cin = Cin; l.Hin = Hin; l.Win = Win; l.KH = KH; l.KW = KW; l.stride = stride; l.pad = pad;
+    l.Csrc = 1; l.flags = flags;
+    FwdLayerDev d{};
+    size_t lds = 0;
+    int TM = 128;
+    if (const int rc = fwd_describe(l, d, lds, TM); rc != PLEAS_OK) return rc;
+    if (((uintptr_t)w & 15) != 0 || ((uintptr_t)x & 15) != 0) return bad_arg("conv2d_bn_stats_fwd: x and w must be 16-byte aligned");
+    const int64_t per_batch = (int64_t)(N / batches) * d.HWo;      // values per channel and batch
+    if (per_batch <= 1) return bad_arg("conv2d_bn_stats_fwd: more than one value per channel is needed");
+    // a tile has two segments: it may touch two batches, not three
+    if (batches > 1 && per_batch < fTN)
+        return bad_arg("conv2d_bn_stats_fwd: batches of fewer than 128 pixels cannot share a forward (fold them after pleas_conv2d_fwd)");
+    const size_t need = pleas_conv2d_bn_stats_ws_bytes(N, Cout, d.Hout, d.Wout, batches);
+    if (!ws || ws_bytes < need) return workspace_too_small("conv2d_bn_stats_fwd", need);
+    if ((uintptr_t)ws & 7) return bad_arg("conv2d_bn_stats_fwd: workspace must be 8-byte aligned");
+    double* sums = (double*)ws;
+    double* tile_part = sums + conv_bn_stats_head(Cout, batches);
+    if (const int rc = conv2d_launch(x, w, bias, y, nullptr, nullptr, nullptr, nullptr, 0, N, Cin, Hin, Win, Cout, KH, KW, stride, pad,
+                                     flags, stream_, false, tile_part, (uint32_t)per_batch);
+        rc != PLEAS_OK)
+        return rc;
+    return bn_fold_tile_partials(tile_part, fTN, d.Ptot, (uint32_t)per_batch, Cout, batches, sums, gamma, beta, eps, momentum,
+                                 running_mean, running_var, num_batches_tracked, scale, shift, (hipStream_t)stream_);
 }
 
 // The calibration launch's events: all complete?  Then the plan's units take their measured durations, long ones are cut and

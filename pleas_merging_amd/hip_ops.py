@@ -907,6 +907,86 @@ def conv2d_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], s
     return z
 
 
+CONV_BN_STATS_TILE = 128      # output pixels of a work item of the convolution kernels (fTN, csrc/conv_fwd.hip)
+
+
+def conv2d_bn_stats_takes(N: int, Cout: int, Ho: int, Wo: int, batches: int) -> str:
+    """What ``pleas_conv2d_bn_stats_fwd`` makes of an ``[N, Cout, Ho, Wo]`` output in ``batches`` batches, from host arithmetic:
+    ``"fused"``; ``"straddle"`` -- batches of fewer than 128 pixels share the forward, a tile would touch more than two of them:
+    fold after ``conv2d``; ``"limits"`` -- over the per-call limits of the convolution kernels, or nothing to normalise."""
+    if N <= 0 or Ho <= 0 or Wo <= 0 or batches < 1 or N % batches or N * Ho * Wo >= CONV_MAX_PIXELS or N * Ho * Wo * Cout >= CONV_MAX_OUTPUT:
+        return "limits"
+    per_batch = N // batches * Ho * Wo
+    if per_batch <= 1:
+        return "limits"
+    return "straddle" if batches > 1 and per_batch < CONV_BN_STATS_TILE else "fused"
+
+
+class ConvBnStats:
+    """``conv2d`` + ``BnTrainFold`` as ONE call of ``pleas_conv2d_bn_stats_fwd`` for one train-mode BatchNorm2d called forward after
+    forward (graph callable of the BN-reset pass): the convolution's work items leave the sums of their tile's outputs, so ``y`` is
+    not read back for its statistics.  Workspace, the ``[2][batches][C]`` outputs and the module's addresses are looked up once per
+    input shape; ``bn.momentum`` is read per call.  The returned ``(scale, shift)`` are views of a buffer that the NEXT call
+    overwrites (as ``BnTrainFold``'s); ``y`` is a fresh tensor."""
+
+    def __init__(self, bn: "torch.nn.BatchNorm2d"):
+        self.bn = bn
+        self._shape = None
+
+    def _addresses(self) -> tuple:
+        return BnTrainFold._addresses(self)
+
+    def _prepare(self, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, kpos_major: bool, batches: int) -> None:
+        bn = self.bn
+        N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d_bn_stats", x, w, stride, pad, kpos_major)
+        if N % batches:
+            raise PleasHipError("conv2d_bn_stats: %d samples do not split into %d batches" % (N, batches))
+        if N // batches * max(Ho, 0) * max(Wo, 0) <= 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % ((N // batches, Cout, Ho, Wo),))
+        track = bn.track_running_stats and bn.running_mean is not None
+        tensors = (bn.weight, bn.bias) + ((bn.running_mean, bn.running_var, bn.num_batches_tracked) if track else (None, None, None))
+        for t in tensors[:4]:
+            # (the tensors' own length: a merged model's modules keep the `num_features` they were built with)
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device or t.numel() != Cout):
+                raise PleasHipError("conv2d_bn_stats: BatchNorm parameters / buffers must be contiguous fp32 vectors of %d "
+                                    "channels on x's device" % Cout)
+        g, b, rm, rv, nbt = (t.data_ptr() if t is not None else None for t in tensors)
+        need = int(_lib.lib().pleas_conv2d_bn_stats_ws_bytes(N, Cout, Ho, Wo, batches))
+        self._ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+        self._out = torch.empty(2, batches, Cout, dtype=torch.float32, device=x.device)
+        self._tensors = self._addresses()
+        self._geo = (N, Cin, H, W, Cout, KH, KW, stride, pad, FwdBatch.KPOS_MAJOR if kpos_major else 0, batches)
+        self._bn_args = (g, b, float(bn.eps))
+        self._tail = (rm, rv, nbt, self._out[0].data_ptr(), self._out[1].data_ptr(), self._ws.data_ptr(), need)
+        self._y_shape = (N, Cout, Ho, Wo)
+        self._shape = (tuple(x.shape), tuple(w.shape), x.device, stride, pad, kpos_major, batches)
+
+    def __call__(self, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int,
+                 kpos_major: bool = False, batches: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(y, scale, shift)``: ``y = conv2d(x, w, bias)``; ``x`` holds ``batches`` batches back to back along dim 0, each folded
+        on its own samples, in order -- ``scale`` / ``shift`` are ``[C]`` for one batch, ``[batches, C]`` for several."""
+        _need_gpu(x, w)
+        if self._shape != (tuple(x.shape), tuple(w.shape), x.device, stride, pad, kpos_major, batches) or self._tensors != self._addresses():
+            self._prepare(x, w, stride, pad, kpos_major, batches)
+        bn = self.bn
+        y = torch.empty(self._y_shape, dtype=torch.float32, device=x.device)
+        g, b, eps = self._bn_args
+        rc = _lib.lib().pleas_conv2d_bn_stats_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                                  y.data_ptr(), *self._geo, g, b, eps,
+                                                  -1.0 if bn.momentum is None else float(bn.momentum), *self._tail, _stream())
+        check(rc, "pleas_conv2d_bn_stats_fwd")
+        return (y, self._out[0, 0], self._out[1, 0]) if batches == 1 else (y, self._out[0], self._out[1])
+
+
+def conv2d_bn_stats(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int, kpos_major: bool,
+                    bn: "torch.nn.BatchNorm2d", batches: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``y = conv2d(x, w, bias)`` and train-mode ``bn`` on ``y`` as ``bn_train_fold`` returns it -- ``(y, scale, shift)``, ``bn``'s
+    running statistics and counter moved on -- from ONE call (``pleas_conv2d_bn_stats_fwd``): ``y`` bit for bit ``conv2d``'s, its
+    statistics taken in the convolution's epilogue.  One-off form of ``ConvBnStats``."""
+    y, scale, shift = ConvBnStats(bn)(x, w, bias, stride, pad, kpos_major, batches)
+    return y, scale.clone(), shift.clone()
+
+
 def channel_map(index, channels: int, device) -> torch.Tensor:
     """A channel map for ``pool_gather``: ``index`` (any integer sequence / tensor) as a contiguous int32 tensor on ``device``,
     its entries checked against ``[0, channels)`` on the HOST, once -- ``pool_gather`` takes it without looking again."""

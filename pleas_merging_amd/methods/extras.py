@@ -26,26 +26,35 @@ from torch import nn
 from ..core.utils import Axis, Permutation, PermutationSpec
 
 
-def _bn_reset_runner(model: nn.Module, fused: bool):
+BN_RESET_BACKBONES = ("modules", "hip")
+
+
+def _bn_reset_runner(model: nn.Module, fused: bool, backbone: str = "modules"):
     """What the pass forwards: on the GPU, an fx copy of ``model`` (same submodules, same buffers) whose train-mode
     ``BatchNorm2d -> [+ identity] -> [ReLU]`` chains are ``pleas_bn_train_fold`` + ONE ``pleas_bn_act`` pass each -- the
     statistics kernel moves the module's running statistics and counter as the module would; on the CPU, or when the
-    model cannot be traced, the model itself (vendor modules)."""
+    model cannot be traced, the model itself (vendor modules).  ``backbone="hip"``: the graph's convolutions are the library's own
+    as well (``fuse_bn_act(train_convs=True)``): a convolution followed by a train-mode BatchNorm leaves that BatchNorm's batch
+    statistics from its epilogue (``HipConvBnStats``) -- no vendor convolution, so the pass is bit-for-bit repeatable."""
     if fused and next(iter(model.parameters())).is_cuda:
         from .source_forward import fuse_bn_act
 
-        return fuse_bn_act(model, train_stats=True) or model
+        return fuse_bn_act(model, train_stats=True, train_convs=backbone == "hip") or model
     return model
 
 
 @torch.no_grad()
 def reset_bn_stats(model: nn.Module, dataloader: Iterable, num_batches: int = 101, device=None, shard: bool = True,
-                   fused: bool = True, batches_per_forward=None) -> nn.Module:
+                   fused: bool = True, batches_per_forward=None, backbone: str = "modules") -> nn.Module:
     """Recompute BatchNorm running statistics of a (merged) model on data.
 
     ``fused=True`` (default): a model on the GPU is forwarded through the HIP BatchNorm path (``_bn_reset_runner``);
     ``fused=False`` runs the vendor modules (what the reference's loop does, kept for A/B).  ``batches_per_forward``
     (HIP path, one process): consecutive equal batches per forward, each still normalised and counted on its own.
+    ``backbone`` (with ``fused``, a model on the GPU; one process and data parallel alike): ``"modules"`` (default) leaves the
+    convolutions to the vendor's kernels, whose 3 x 3 picks split K with atomics -- two runs of the pass differ in the last bits;
+    ``"hip"`` runs them on the library's own kernels, batch statistics taken in their epilogues: the same call returns the same
+    bits.  A model on the CPU runs its modules under either value; anything else raises ``ValueError``.
 
     Same procedure as the reference drivers: ``model.train()``, ``reset_running_stats()`` on every
     ``BatchNorm2d``, ``num_batches`` forward passes without gradients (the drivers break after 101),
@@ -60,6 +69,8 @@ def reset_bn_stats(model: nn.Module, dataloader: Iterable, num_batches: int = 10
     """
     from .activation_matching import _dist_info
 
+    if backbone not in BN_RESET_BACKBONES:
+        raise ValueError("reset_bn_stats: backbone must be one of %r, got %r" % (BN_RESET_BACKBONES, backbone))
     if device is None:
         device = next(iter(model.parameters())).device
     rank, world = _dist_info() if shard else (0, 1)
@@ -67,7 +78,7 @@ def reset_bn_stats(model: nn.Module, dataloader: Iterable, num_batches: int = 10
     bns = [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
     for m in bns:
         m.reset_running_stats()
-    runner = _bn_reset_runner(model, fused)        # built AFTER model.train(): the rewrite folds what is in train mode
+    runner = _bn_reset_runner(model, fused, backbone)        # built AFTER model.train(): the rewrite folds what is in train mode
     if world == 1:
         # HIP path: consecutive batches of equal shape share a forward (the vendor convolutions run faster per sample on
         # 64 samples than on 16) -- every BatchNorm still folds each batch on its own samples, in order, in one launch, so

@@ -11,6 +11,10 @@ be fused.  ``fuse_bn_act`` rewrites an fx trace of the model:
     bn(x) -> relu -> MaxPool2d         =>  bn_act_maxpool(x, scale, shift, kernel, stride, padding, relu=True)
                                            (the stem: the full-resolution ReLU output is never written)
 
+    (train mode, ``train_convs=True``)
+    HipConv(conv)(x) -> bn_train_fold  =>  HipConvBnStats: ONE call that stores the convolution's output and folds its batch statistics,
+                      + bn_act(...)        taken in the convolution's epilogue (``hip_ops.ConvBnStats``); the activation pass follows
+
     Conv2d (k x k, dense, undilated)   =>  HipConv(conv)(x): ``hip_ops.conv2d`` -- the grouped forward's tile forms as a plain
                                            convolution, bit-for-bit repeatable (``SOURCE_CONV``)
     HipConv(conv)(x) -> bn_act(...)    =>  HipConvBnAct: ONE launch that stores the convolution's output (the hooks' tensor) and
@@ -334,12 +338,97 @@ def _train_fold(bn: nn.BatchNorm2d, tag: str, state: Optional[BatchesPerForward]
         return folder(x, state.parts if state is not None else 1)
 
     fold.__name__ = fold.__qualname__ = "bn_train_fold_%s" % tag
+    fold.train_fold_of = (bn, folder, state)      # read by the pass that pairs the fold with its convolution
     return fold
+
+
+class HipConvBnStats:
+    """Graph callable ``x -> (y, scale, shift)`` for an own convolution whose only consumers are ONE train-mode BatchNorm fold and
+    that chain's ``bn_act`` / ``bn_act_pool``: ``hip_ops.ConvBnStats`` -- the convolution leaves its output's batch statistics from
+    its epilogue, the running statistics and the counter move as in the module's forward, ``y`` is not read back for them.
+    ``state.parts`` batches share the tensor, each folded on its own samples.  Taken apart again, call by call:
+
+    * CPU tensors, autograd on, a shape over the kernels' per-call limits: the convolution MODULE, then the fold of its output;
+    * batches of fewer than 128 pixels sharing a forward (a tile would touch more than two), or forward hooks on the convolution
+      (they get ``y`` and may replace it before it is normalised): ``HipConv`` then ``BnTrainFold`` -- two launches.
+
+    ``taken`` counts the calls per path ("fused" / "two_launch" / "module")."""
+
+    def __init__(self, own: HipConv, bn: nn.BatchNorm2d, tag: str, state: Optional[BatchesPerForward] = None,
+                 folder: Optional["hip_ops.BnTrainFold"] = None):
+        self.own, self.bn, self.state = own, bn, state
+        self.folder = folder if folder is not None else hip_ops.BnTrainFold(bn)
+        self.fused = hip_ops.ConvBnStats(bn)
+        self.taken = {"fused": 0, "two_launch": 0, "module": 0}
+        self.__name__ = self.__qualname__ = "hip_conv_%s_bn_stats" % tag
+
+    def _path(self, x, parts: int) -> str:
+        own, conv = self.own, self.own.conv
+        if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not conv.weight.is_cuda
+                or (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad))):
+            return "module"
+        N, _, H, W = x.shape
+        Ho, Wo = (H + 2 * own.pad - own.k) // own.stride + 1, (W + 2 * own.pad - own.k) // own.stride + 1
+        takes = hip_ops.conv2d_bn_stats_takes(N, conv.weight.shape[0], Ho, Wo, parts)
+        if takes == "limits":
+            return "module"
+        return "two_launch" if takes == "straddle" or (own.fire_hooks and conv._forward_hooks) else "fused"
+
+    def __call__(self, x):
+        own, conv = self.own, self.own.conv
+        parts = self.state.parts if self.state is not None else 1
+        path = self._path(x, parts)
+        self.taken[path] += 1
+        if path != "fused":
+            y = conv(x) if path == "module" else own(x)
+            return (y,) + tuple(self.folder(y, parts))
+        return self.fused(x if x.is_contiguous() else x.contiguous(), own.weight(), conv.bias, own.stride, own.pad, own.kpos, parts)
+
+
+def _own_convs(graph: torch.fx.Graph, mods, conv: Optional[str]) -> int:
+    """Every Conv2d call that ``own_conv_ok`` takes becomes a ``HipConv`` call; returns how many."""
+    swapped = 0
+    for node in list(graph.nodes):
+        if node.op == "call_module" and len(node.args) == 1 and not node.kwargs and own_conv_ok(mods.get(node.target), conv):
+            with graph.inserting_before(node):
+                own = graph.create_node("call_function", HipConv(mods[node.target], node.name), (node.args[0],), {}, name=node.name + "_hip")
+            node.replace_all_uses_with(own)
+            graph.erase_node(node)
+            swapped += 1
+    return swapped
+
+
+def _conv_stats_pairs(graph: torch.fx.Graph, op: Callable, pool_op: Optional[Callable]) -> None:
+    """``HipConv(x)`` consumed by one train-mode fold and by that fold's ``op`` / ``pool_op`` call, and by nothing else, becomes
+    ONE ``HipConvBnStats`` call whose three results feed the activation pass."""
+    for stats in list(graph.nodes):
+        if not (stats.op == "call_function" and hasattr(stats.target, "train_fold_of") and isinstance(stats.args[0], torch.fx.Node)):
+            continue
+        src = stats.args[0]
+        if not (src.op == "call_function" and type(src.target) is HipConv):
+            continue
+        maps = set(stats.users)                                     # the getitem nodes: scale, shift
+        acts = [u for u in src.users if u is not stats]
+        if not (len(acts) == 1 and acts[0].op == "call_function" and acts[0].target in (op, pool_op) and acts[0].args[0] is src
+                and all(m.op == "call_function" and m.target is operator.getitem and set(m.users) == {acts[0]} for m in maps)
+                and src not in acts[0].args[1:]):
+            continue
+        bn, folder, state = stats.target.train_fold_of
+        tag = src.target.__name__[len("hip_conv_"):]
+        with graph.inserting_before(src):
+            both = graph.create_node("call_function", HipConvBnStats(src.target, bn, tag, state, folder), (src.args[0],), {},
+                                     name=src.name + "_bn_stats")
+            y = graph.create_node("call_function", operator.getitem, (both, 0), {}, name=src.name + "_y")
+        for m in maps:                                              # (scale, shift) move one place up
+            m.args = (both, m.args[1] + 1)
+        acts[0].replace_input_with(src, y)
+        graph.erase_node(stats)
+        graph.erase_node(src)
 
 
 def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = False,
                 pool_op: Optional[Callable] = None, conv: Optional[str] = None,
-                inference: bool = False) -> Optional[torch.fx.GraphModule]:
+                inference: bool = False, train_convs: bool = False) -> Optional[torch.fx.GraphModule]:
     """fx copy of ``model`` (sharing its submodules) with every eval-mode BatchNorm2d chain replaced by
     ``op(x, scale, shift, residual_or_None, relu)`` -- the HIP kernel ``hip_ops.bn_act`` unless a test
     passes its own.  Returns None when the model cannot be traced or holds nothing to fold; the caller
@@ -354,12 +443,17 @@ def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = Fa
     pooling (``hip_ops.bn_act_maxpool`` with the default ``op``; with a caller's ``op`` only when passed too).
 
     ``conv`` ("kxk" / "all" / "vendor", default ``SOURCE_CONV``): which Conv2d calls become ``HipConv`` calls -- only with
-    the default ``op`` (a test's CPU ``op`` keeps the modules) and never for a model in train mode (autograd may be on).
+    the default ``op`` (a test's CPU ``op`` keeps the modules) and, unless ``train_convs`` asks for it, never for a model in train mode (autograd may be on).
 
     ``inference=True`` (default ``op``, model in eval mode): the graph of a forward that nobody taps -- every ``HipConvBnAct``
     becomes the image-only ``HipConvAct`` (a convolution that carries hooks when it is called still hands them its output),
     ``AdaptiveAvgPool2d((1, 1))`` -> ``flatten(1)`` becomes one ``PoolGather``, an ``nn.Linear`` on its result the own
-    ``HipLinear``, and ``nn.Identity`` calls are dropped.  The stem and whatever is not recognised stay as in the default graph."""
+    ``HipLinear``, and ``nn.Identity`` calls are dropped.  The stem and whatever is not recognised stay as in the default graph.
+
+    ``train_convs=True`` (default ``op``, model in TRAIN mode, with ``train_stats``; an explicit opt-in -- the BN-statistics reset
+    with ``backbone="hip"``): the Conv2d calls of a train-mode graph become ``HipConv`` calls too -- ``HipConv`` declines under
+    autograd call by call -- and a convolution consumed by one train-mode fold and that chain's activation pass alone becomes ONE
+    ``HipConvBnStats`` call.  Without it the function builds the graph it always built."""
     if pool_op is None and op is _bn_act:
         pool_op = _bn_act_pool
     try:
@@ -419,14 +513,12 @@ def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = Fa
         for dead in reversed(chain):
             graph.erase_node(dead)
         folded += 1
+    if op is _bn_act and model.training and train_convs:
+        folded += _own_convs(graph, mods, conv)
+        if train_stats:
+            _conv_stats_pairs(graph, op, pool_op)
     if op is _bn_act and not model.training:
-        for node in list(graph.nodes):
-            if node.op == "call_module" and len(node.args) == 1 and not node.kwargs and own_conv_ok(mods.get(node.target), conv):
-                with graph.inserting_before(node):
-                    own = graph.create_node("call_function", HipConv(mods[node.target], node.name), (node.args[0],), {}, name=node.name + "_hip")
-                node.replace_all_uses_with(own)
-                graph.erase_node(node)
-                folded += 1
+        folded += _own_convs(graph, mods, conv)
         if SOURCE_CONV_BN == "1":
             # an own convolution consumed by one eval-mode chain only (constants, not per-batch statistics): one launch
             for node in list(graph.nodes):
