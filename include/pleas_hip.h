@@ -323,6 +323,37 @@ int pleas_sqerr(const float* a, const float* b, int64_t n, float scale, int accu
 int pleas_channel_sum(const float* x, int N, int C, int64_t HW, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Forward of an nn.Linear: y[n][c] = bias[c] + sum_k x[n][k] * w[c][k]   (csrc/linear.hip).
+ *
+ * Replaces: `fc(feats)` of the linear probe's step and of the merged model's classifier (pleas/methods/pleas_merging.py:499-570,
+ *   :469-496), which the library ran through pleas_conv2d_fwd with H = W = KH = KW = 1 -- a convolution tile on one pixel per
+ *   sample.  Here: one 64 x 64 NT tile form whose K axis is cut into S ranges of whole 32-float chunks, S a pure function of
+ *   (N, C, K) that brings the grid to about two workgroups per CU.
+ * Layout: x [N][K], w [C][K], y [N][C], all row-major contiguous fp32; bias fp32[C] or NULL.  Any 4-byte alignment is legal:
+ *   16-byte loads when K % 4 == 0 and x and w are 16-byte aligned, 4-byte loads otherwise (same results).
+ * Workspace: ws of at least pleas_linear_ws_bytes(N, C, K) bytes, the partial tiles [S][N][C]; 0 bytes (ws may be NULL) when
+ *   S == 1, where the tile writes y itself and no second grid runs.  The call leaves nothing in ws that a later call needs.
+ * Determinism: the slabs are added in slab order, then the bias, by a second grid; no floating-point atomics.  The same call
+ *   gives the same bits.
+ * Arithmetic: exact fp32 MFMA in EVERY pleas_arith mode; the switch does not reach this kernel.
+ * Limits: x, w and y each hold fewer than 2^30 elements (PLEAS_EINVAL otherwise).  Negative sizes, a NULL y, or a NULL x / w with
+ *   K > 0: PLEAS_EINVAL; a workspace that is too small: PLEAS_ENOMEM; all before anything is enqueued.  N == 0 (or C == 0):
+ *   PLEAS_OK, nothing is enqueued.  K == 0: y = bias, or zeros.
+ * pleas_linear_plan_info: info[0 .. 4] = sample tiles, class tiles, S, chunks per range, chunks of the last range (host
+ *   arithmetic only: no device is touched).  Ranges 0 .. S-2 hold `chunks per range` chunks each; none is empty. */
+size_t pleas_linear_ws_bytes(int64_t N, int C, int K);
+int pleas_linear_plan_info(int64_t N, int C, int K, int* info);
+int pleas_linear_fwd(const float* x, const float* w, const float* bias, float* y, int64_t N, int C, int K, void* ws,
+                     size_t ws_bytes, void* stream);
+
+/* Bias gradient of a Linear: out[c] = sum_n x[n][c] for x [N][C] contiguous fp32, out fp32[C].
+ * Replaces the bias node of autograd's backward for a Linear (pleas_channel_sum with HW = 1 walks the N rows with one thread).
+ * Row-parallel: lanes run along c, a thread adds a fixed stripe of rows (n = stripe, stripe + 32, ...) in increasing n, the 32
+ * stripes of a column are added in stripe order.  Deterministic, no atomics.  C = 1 and N = 1 are legal; N <= 0, C <= 0 or
+ * N * C >= 2^30: PLEAS_EINVAL. */
+int pleas_column_sum(const float* x, int64_t N, int C, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * PLeaS layer fitting: fused target/residual/loss pass and grouped weight-gradient launch.
  *
  * Replaces, for merging='perm_gradmask': the output half of get_model_orig_activations

@@ -1,4 +1,4 @@
-// The NT contraction tile of gram_tile, wgrad_tile, neq_tile, neq_lag_tile and the forward convolution's fwd_tile / fwd_flat_tile
+// The NT contraction tile of gram_tile, wgrad_tile, neq_tile, neq_lag_tile, lin_tile and the forward convolution's fwd_tile / fwd_flat_tile
 // (DESIGN.md 3.1), device side: C[i][j] += sum_k A[i][k] * B[j][k] on a TM x TN tile.  256 threads = 2 x 2 waves, each wave
 // (wm, wn) owns a TM/2 x TN/2 quarter as 32 x 32 MFMA tiles.  A K chunk of 32 goes global -> registers -> LDS; the kernels'
 // loaders (what differs between them) stay with them.

@@ -9,6 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import math
+import os
 import threading
 from typing import List, Optional, Sequence, Tuple
 
@@ -825,6 +826,84 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], strid
     check(_lib.lib().pleas_conv2d_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
                                       N, Cin, H, W, Cout, KH, KW, stride, pad, FwdBatch.KPOS_MAJOR if kpos_major else 0,
                                       _stream()), "pleas_conv2d_fwd")
+    return out
+
+
+# ---------------------------------------------------------------------------------------- Linear
+# Which kernel an nn.Linear the library runs itself goes through (the probe's head, the inference graph's classifier):
+#   "conv"  ``pleas_conv2d_fwd`` with H = W = KH = KW = 1 on 4-D views, and ``channel_sum`` for the bias gradient: the calls and
+#           the bits of every release so far (the default)
+#   "gemm"  ``pleas_linear_fwd``, the split-K NT tile of csrc/linear.hip, and ``column_sum``
+# Both are deterministic.  ``PLEAS_LINEAR`` in the environment sets the process's form, ``linear_form`` a block's.
+LINEAR_FORMS = ("conv", "gemm")
+
+
+def _linear_form_checked(mode) -> str:
+    if mode not in LINEAR_FORMS:
+        raise ValueError("linear form %r is not one of %s" % (mode, LINEAR_FORMS))
+    return mode
+
+
+LINEAR = _linear_form_checked(os.environ.get("PLEAS_LINEAR", "conv"))
+
+
+@contextlib.contextmanager
+def linear_form(mode: str):
+    """``LINEAR = mode`` for the block, the previous form again afterwards (also when the block raises).  Process-wide, as
+    ``arith``: not for blocks that run beside other threads' launches."""
+    global LINEAR
+    before, LINEAR = LINEAR, _linear_form_checked(mode)
+    try:
+        yield
+    finally:
+        LINEAR = before
+
+
+def linear_plan_info(N: int, C: int, K: int) -> Tuple[int, int, int, int, int]:
+    """``(sample tiles, class tiles, S, chunks per K range, chunks of the last range)`` of ``pleas_linear_fwd``; host only."""
+    info = (ctypes.c_int * 5)()
+    check(_lib.lib().pleas_linear_plan_info(N, C, K, info), "pleas_linear_plan_info")
+    return tuple(info)
+
+
+def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``F.linear(x, w, bias)`` for fp32 ``x`` [N, K] and contiguous ``w`` [C, K] on the GPU, into ``out`` [N, C] when given.
+    The kernel is the one ``LINEAR`` names.  A non-contiguous ``x`` is copied first; under "conv" so is a ``x`` that is not
+    16-byte aligned (what the two callers of ``conv2d`` did), under "gemm" it is read where it lies with 4-byte loads."""
+    _need_gpu(x, w)
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1] or w.device != x.device or not w.is_contiguous():
+        raise PleasHipError("linear: x [N, K] and a contiguous w [C, K] on one device expected, got %s and %s on %s / %s"
+                            % (tuple(x.shape), tuple(w.shape), x.device, w.device))
+    (N, K), C = x.shape, w.shape[0]
+    if bias is not None and (bias.device != x.device or bias.dtype != torch.float32 or bias.numel() != C or not bias.is_contiguous()):
+        raise PleasHipError("linear: bias must be a contiguous fp32 tensor of %d elements on the operands' device" % C)
+    if out is None:
+        out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    elif out.device != x.device or out.dtype != torch.float32 or tuple(out.shape) != (N, C) or not out.is_contiguous():
+        raise PleasHipError("linear: out must be a contiguous fp32 tensor of shape (%d, %d) on the operands' device" % (N, C))
+    form = LINEAR
+    if not x.is_contiguous() or (form == "conv" and x.data_ptr() % 16):
+        x = x.clone(memory_format=torch.contiguous_format)
+    if form == "conv":
+        conv2d(x.view(N, K, 1, 1), w.view(C, K, 1, 1), bias, 1, 0, out=out.view(N, C, 1, 1))
+        return out
+    need = int(_lib.lib().pleas_linear_ws_bytes(N, C, K))
+    ws = Workspace.get(x.device).reserve(need) if need else None
+    check(_lib.lib().pleas_linear_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
+                                      N, C, K, ws.data_ptr() if need else None, ws.numel() if need else 0, _stream()),
+          "pleas_linear_fwd")
+    return out
+
+
+def column_sum(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """``out[c] = sum over n of x[n][c]`` (``x`` [N, C] contiguous fp32, N, C >= 1): the bias gradient of a Linear from the
+    gradient of its output, row-parallel (``pleas_column_sum``)."""
+    _need_gpu(x, out)
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[0] < 1 or x.shape[1] < 1:
+        raise PleasHipError("column_sum: x must be a contiguous, non-empty [N, C] tensor, got %s" % (tuple(x.shape),))
+    if out.device != x.device or out.numel() != x.shape[1] or not out.is_contiguous():
+        raise PleasHipError("column_sum: out must hold %d contiguous floats on x's device" % x.shape[1])
+    check(_lib.lib().pleas_column_sum(x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), _stream()), "pleas_column_sum")
     return out
 
 

@@ -2,8 +2,9 @@
 
 Reference: pleas/methods/pleas_merging.py:499-570 trains a fresh ``nn.Linear`` on frozen features with Adam, a cosine schedule
 and cross entropy on autograd: about fifteen small launches per step and one ``float(loss)`` read-back.  Here one step is five
-launches of kernels the library owns -- the head's forward (``hip_ops.conv2d`` with H = W = 1), ``hip_ops.softmax_xent`` (loss,
-``dlogits`` and the hit count from one pass), one ``WgradBatch`` with the single Linear layer, ``channel_sum`` for the bias
+launches of kernels the library owns -- the head's forward (``hip_ops.linear``: ``conv2d`` with H = W = 1, or the split-K GEMM
+under ``hip_ops.linear_form("gemm")``, which adds a slab-reduce launch), ``hip_ops.softmax_xent`` (loss, ``dlogits`` and the hit
+count from one pass), one ``WgradBatch`` with the single Linear layer, ``channel_sum`` (``column_sum`` under "gemm") for the bias
 gradient and one ``masked_adam`` over the whole parameter arena -- and nothing is read back before the epoch ends.
 """
 from __future__ import annotations
@@ -73,9 +74,7 @@ class HipProbeHead:
         return feats.clone(memory_format=torch.contiguous_format)
 
     def _forward(self, feats: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-        N = feats.shape[0]
-        hip_ops.conv2d(feats.view(N, self.D, 1, 1), self.w.view(self.C, self.D, 1, 1), self.b, 1, 0, out=out.view(N, self.C, 1, 1))
-        return out
+        return hip_ops.linear(feats, self.w, self.b, out=out)
 
     def logits(self, feats: torch.Tensor) -> torch.Tensor:
         """``feats @ W.T + b`` as a fresh [N, C] tensor (the test loop: ``top1_count(head.logits(f), y, head.counts[:1])``)."""
@@ -99,7 +98,7 @@ class HipProbeHead:
         wgrad.add(dlogits, feats, self.gw)
         wgrad.flush()
         if self.gb is not None:
-            hip_ops.channel_sum(dlogits, self.gb)
+            (hip_ops.column_sum if hip_ops.LINEAR == "gemm" else hip_ops.channel_sum)(dlogits, self.gb)
         hip_ops.masked_adam(self.p, self.g, None, self.m, self.v, lr, t)
 
     def epoch_readback(self) -> Tuple[int, int, float, float]:

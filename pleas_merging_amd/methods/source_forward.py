@@ -173,8 +173,9 @@ class PoolGather:
 
 
 class HipLinear:
-    """Graph callable standing in for an ``nn.Linear`` on 2-D features: ``hip_ops.conv2d`` with H = W = KH = KW = 1 on views
-    (no copy of the weight: the parameter is read where it is).  The module itself for anything else."""
+    """Graph callable standing in for an ``nn.Linear`` on 2-D features: ``hip_ops.linear`` (``conv2d`` with H = W = KH = KW = 1
+    on views, or the GEMM form under ``hip_ops.linear_form("gemm")``; no copy of the weight: the parameter is read where it is).
+    The module itself for anything else."""
 
     def __init__(self, fc: nn.Linear, tag: str):
         self.fc = fc
@@ -187,9 +188,7 @@ class HipLinear:
                 or not w.is_contiguous() or w.data_ptr() % 16
                 or (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
             return fc(x)
-        x = x if x.is_contiguous() and x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
-        y = hip_ops.conv2d(x.view(x.shape[0], x.shape[1], 1, 1), w.detach().view(w.shape[0], w.shape[1], 1, 1), fc.bias, 1, 0)
-        return y.view(x.shape[0], w.shape[0])
+        return hip_ops.linear(x, w.detach(), fc.bias)
 
 
 def _is_global_avgpool(node: torch.fx.Node, mods) -> bool:

@@ -3,15 +3,18 @@
 batches of 64 and 256, everything device-resident.
 
 1. The head alone: one training step on a fixed feature batch -- ``head="hip"`` (``HipProbeHead.step``: own Linear forward,
-   ``softmax_xent``, one grouped weight gradient, ``channel_sum``, ``masked_adam``) against the autograd step of the default path
+   ``softmax_xent``, one grouped weight gradient, ``channel_sum``, ``masked_adam``), once per form of ``hip_ops.linear`` (leg
+   ``hip``: "conv", the default; leg ``hip_gemm``: ``linear_form("gemm")``), against the autograd step of the default path
    (Linear, cross entropy, backward, Adam, the scheduler, argmax / compare / sum), the latter with and without the
    ``float(loss)`` read-back that path does every step.  ``--warmup`` steps, then ``--repeats`` windows of ``--steps`` steps per
    leg, the legs alternating; HIP events around a window and a synchronise.
 2. A whole ``--epochs``-epoch probe on a ResNet-50 under ``backbone="hip"`` over ``--batches`` batches per epoch (and 2 test
-   batches): both heads, with and without ``cache_features``; one warm-up call (1 epoch) per leg, then ``--repeats`` timed calls.
+   batches): the heads (``hip`` again under both forms), with and without ``cache_features`` (``--probe-legs`` picks legs by
+   name, e.g. the three ``*/cache`` ones); one warm-up call (1 epoch) per leg, then ``--repeats`` timed calls.
 
-``--profile-steps N`` instead runs N ``head="hip"`` steps per batch size, untimed: run it under
-``rocprofv3 --kernel-trace --stats -- python tools/probe_bench.py --profile-steps 100`` to read each kernel's share of a step.
+``--profile-steps N`` instead runs N ``head="hip"`` steps per batch size and form, untimed: run it under
+``rocprofv3 --kernel-trace --stats -- python tools/probe_bench.py --profile-steps 100`` to read each kernel's share of a step
+(the two forms' forward and bias-gradient kernels have names of their own, the other kernels run 2 N times).
 
 Prints one JSON line and, with ``--out``, writes it to a file.
 Run on the GPU box under a time limit:  timeout -k 10 900 python tools/probe_bench.py --out profiles/probe_bench.json
@@ -41,22 +44,26 @@ def timed(fn):
 
 
 def head_legs(batch, lr=1e-3):
-    """name -> ``run(steps)`` of the three head legs on one fixed batch; every leg owns its head and optimiser state."""
+    """name -> ``run(steps)`` of the four head legs on one fixed batch; every leg owns its head and optimiser state."""
+    from pleas_merging_amd import hip_ops
     from pleas_merging_amd.methods.linear_probe import HipProbeHead
 
     g = torch.Generator().manual_seed(batch)
     feats = torch.randn(batch, D, generator=g).cuda()
     labels = torch.randint(0, C, (batch,), generator=g).cuda()
 
-    torch.manual_seed(0)
-    hip = HipProbeHead(nn.Linear(D, C).cuda())
-    state = {"t": 0}
+    def hip_head(form):
+        torch.manual_seed(0)
+        hip = HipProbeHead(nn.Linear(D, C).cuda())
+        state = {"t": 0}
 
-    def run_hip(steps):
-        for _ in range(steps):
-            state["t"] += 1
-            hip.step(feats, labels, lr, state["t"])
-        hip.epoch_readback()                       # what an epoch ends with
+        def run(steps):
+            with hip_ops.linear_form(form):
+                for _ in range(steps):
+                    state["t"] += 1
+                    hip.step(feats, labels, lr, state["t"])
+            hip.epoch_readback()                   # what an epoch ends with
+        return run
 
     def autograd(readback):
         torch.manual_seed(0)
@@ -81,7 +88,8 @@ def head_legs(batch, lr=1e-3):
             float(hit)
         return run
 
-    return {"hip": run_hip, "autograd": autograd(True), "autograd_no_readback": autograd(False)}
+    return {"hip": hip_head("conv"), "hip_gemm": hip_head("gemm"), "autograd": autograd(True),
+            "autograd_no_readback": autograd(False)}
 
 
 def backbone_and_data(batch, n_train, seed=0):
@@ -107,14 +115,18 @@ def main():
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batches", type=int, default=8)
     ap.add_argument("--skip-probe", action="store_true")
+    ap.add_argument("--probe-legs", nargs="+", default=None, help="whole-probe legs to time, e.g. hip/cache hip_gemm/cache")
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    from pleas_merging_amd import hip_ops
     from pleas_merging_amd.methods import train_eval_linear_probe
 
     if args.profile_steps:
         for batch in args.batch_sizes:
-            head_legs(batch)["hip"](args.profile_steps)
+            legs = head_legs(batch)
+            legs["hip"](args.profile_steps)
+            legs["hip_gemm"](args.profile_steps)
         torch.cuda.synchronize()
         print(json.dumps({"profile_steps": args.profile_steps, "batch_sizes": args.batch_sizes}))
         return
@@ -135,9 +147,14 @@ def main():
     for batch in ([] if args.skip_probe else args.batch_sizes):
         model, train, test = backbone_and_data(batch, args.batches)
         legs = {"%s/%s" % (head, "cache" if cache else "no_cache"): (head, cache)
-                for head in ("autograd", "hip") for cache in (False, True)}
-        probe = lambda head, cache, epochs: train_eval_linear_probe(model, train, test, C, None, "bench", epochs=epochs,
-                                                                    backbone="hip", head=head, cache_features=cache)
+                for head in ("autograd", "hip", "hip_gemm") for cache in (False, True)}
+        if args.probe_legs:
+            legs = {name: legs[name] for name in args.probe_legs}
+
+        def probe(head, cache, epochs):
+            with hip_ops.linear_form("gemm" if head == "hip_gemm" else "conv"):
+                return train_eval_linear_probe(model, train, test, C, None, "bench", epochs=epochs, backbone="hip",
+                                               head=head.split("_")[0], cache_features=cache)
         for head, cache in legs.values():
             timed(lambda: probe(head, cache, 1))
         seconds = {name: [] for name in legs}
