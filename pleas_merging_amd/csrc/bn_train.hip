@@ -126,7 +126,7 @@ __global__ __launch_bounds__(1024) void bn_train_finalize_kernel(double* __restr
     if (threadIdx.x == 0 && num_batches_tracked) *num_batches_tracked += batches;
 }
 
-// The tiles' partial sums of a convolution that emitted them (conv_fwd.hip, PLAIN == 4) -> one sum per (batch, channel).
+// The tiles' partial sums of a convolution that emitted them (conv_fwd.hip, FwdMode::ConvStats) -> one sum per (batch, channel).
 // Workgroup (channel block, batch): kRedCh channels x kRedRuns runs of consecutive tiles; a thread adds its run's tiles in tile
 // order, thread (channel, 0) then adds the runs in run order -- fixed, no atomics.  Lanes of neighbouring channels read neighbouring
 // 16 bytes.  Many workgroups: ResNet-101's merged layer1 at 64 samples leaves 1568 tiles x 384 channels = 19 MB of partials.

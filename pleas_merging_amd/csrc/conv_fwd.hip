@@ -38,6 +38,23 @@ typedef short s16x8_t __attribute__((ext_vector_type(8)));
 // W tile rows: [TM][kLds] (k contiguous); U tile rows: [fTN pixels][kLds] (k contiguous: a thread's 16 k values of its pixel are one run)
 constexpr int fTN = 128;
 
+// What the epilogue of a tile does: ONE compile-time mode per kernel, so that no mode's kernel carries another's code.
+//   mode       | entry point                | per-row operands | stores
+//   -----------+----------------------------+------------------+-------------------------------------------------------
+//   Fit        | pleas_fwd_batch            | block maps       | residual 2 (out - target) / numel, one loss partial
+//   Conv       | pleas_conv2d_fwd           | none             | y = conv(x, w) + bias
+//   ConvImage  | pleas_conv2d_bn_act_fwd    | scale, shift     | y and z = act(fma(y, scale, shift) (+ identity))
+//   Image      | pleas_conv2d_act_fwd       | scale, shift     | z alone
+//   ConvStats  | pleas_conv2d_bn_stats_fwd  | none             | y, and per tile and channel the sums of y and y^2 (fp64)
+// y goes where Fit's residual goes (`resid`).  z is bn_act_kernel's arithmetic (elementwise.hip) on the value still in registers; the
+// tile sums are what bn_stats_partial_kernel (bn_train.hip) would read y back for, taken from LDS in a fixed order, no atomics.
+enum class FwdMode : int { Fit = 0, Conv = 1, ConvImage = 2, Image = 3, ConvStats = 4 };
+constexpr int fModes = 5;
+constexpr bool fwd_has_target(FwdMode m) { return m == FwdMode::Fit; }
+constexpr bool fwd_has_image(FwdMode m) { return m == FwdMode::ConvImage || m == FwdMode::Image; }
+constexpr bool fwd_stores_y(FwdMode m) { return m != FwdMode::Image; }
+constexpr bool fwd_has_stats(FwdMode m) { return m == FwdMode::ConvStats; }
+
 struct FwdLayerDev {
     const float* ip;      // merged input  [N][Cin][Hin][Win]
     const float* w;       // [Cout][Kd], Kd = Cin*KH*KW
@@ -46,25 +63,21 @@ struct FwdLayerDev {
     const float* o2;
     const int32_t* row1;  // [Cout] block maps of the output axis (-1 = absent)
     const int32_t* row2;
-    float* resid;         // [N][Cout][HWo]
+    float* resid;         // [N][Cout][HWo]: Fit's residual, y of the modes that store it (null under Image)
     int Cout, Cin, Hin, Win, Hout, Wout, KH, KW, stride, pad, Csrc, n_merged;
     uint32_t HWo, Ptot, Kd;
     float dscale;         // 2 / (numel * world)
     int variant;          // bit0: TM == 64, bit1: scalar W loads, bit2: W is kernel-position-major [Cout][KH*KW][Cin],
                           // bit3: flat-shift tile (fwd_flat_tile), bits 4-5: its KIND
     int part_base;        // first loss-partial slot of this layer
-    int bn_relu;          // PLAIN 2 / 3: ReLU after the affine map (+ identity)
-    // PLAIN == 2 (pleas_conv2d_bn_act_fwd): the convolution's output goes to `resid` AND its activated image
-    // z = act(y * bn_scale[co] + bn_shift[co] (+ bn_res)) to `bn_z` -- the BatchNorm / add / ReLU pass that follows a frozen
-    // source's convolution, without reading y back from memory
+    // the image modes: z = act(y * bn_scale[co] + bn_shift[co] (+ bn_res)) to `bn_z`
+    int bn_relu;             // ReLU after the affine map (+ identity)
     const float* bn_scale;   // [Cout]
     const float* bn_shift;   // [Cout]
     const float* bn_res;     // [N][Cout][HWo] or null
     float* bn_z;             // [N][Cout][HWo]
-    // PLAIN == 3 (pleas_conv2d_act_fwd): the same arithmetic, the activated image ALONE is stored (`resid` is null and unused)
-    // PLAIN == 4 (pleas_conv2d_bn_stats_fwd): the output goes to `resid` as under PLAIN == 1, and every work item leaves the sums
-    // of y and y^2 over its tile's live pixels, per output channel, in `st_part` [pixel tile][2][Cout][2] doubles: segment 0 for
-    // the batch the tile's first pixel belongs to, segment 1 for the next one (`st_pb` pixels per batch, >= fTN or all of them)
+    // ConvStats: `st_part` [pixel tile][2][Cout][2] doubles -- segment 0 for the batch the tile's first pixel belongs to, segment 1
+    // for the next one (`st_pb` pixels per batch, >= fTN or all of them)
     double* st_part;
     uint32_t st_pb;
 };
@@ -73,34 +86,29 @@ struct FwdItemDev {
 };
 
 // ---- shared by both tile forms: the epilogue and its per-row operands.  A thread owns the TM / 8 output channels
-// tid / 32 + 8 j of its tile; per channel the epilogue takes two 32-bit values and the bias:
-//   PLAIN 0 / 1: the channel's rows in the two sources' outputs (the block maps; -1 = absent)
-//   PLAIN 2 / 3: the channel's BatchNorm scale and shift (no block maps there)
-template <int TM, int PLAIN>
+// tid / 32 + 8 j of its tile; per channel the epilogue takes two 32-bit values and the bias: the channel's rows in the two sources'
+// outputs (the block maps; -1 = absent), or, in the image modes, its BatchNorm scale and shift
+template <int TM, bool IMAGE>
 struct FwdRowOps {
     int row1[TM / 8], row2[TM / 8];
     float bias[TM / 8];
 };
 template <int TM>
-struct FwdRowOps<TM, 2> {
+struct FwdRowOps<TM, true> {
     float scale[TM / 8], shift[TM / 8];
     float bias[TM / 8];
 };
-template <int TM>
-struct FwdRowOps<TM, 3> : FwdRowOps<TM, 2> {};
-// the modes whose epilogue applies the BatchNorm map (the others take the primary template's block maps)
-constexpr bool fwd_has_image(int plain) { return plain == 2 || plain == 3; }
-template <int TM, int PLAIN = 0>
-__device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0, FwdRowOps<TM, PLAIN>& ops) {
+template <int TM, FwdMode MODE = FwdMode::Fit>
+__device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0, FwdRowOps<TM, fwd_has_image(MODE)>& ops) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int j = 0; j < TM / 8; ++j) {
         const int co = min(i0 + (tid >> 5) + 8 * j, L.Cout - 1);
-        if constexpr (fwd_has_image(PLAIN)) {
+        if constexpr (fwd_has_image(MODE)) {
             ops.scale[j] = PLEAS_GLOBAL(L.bn_scale)[co];
             ops.shift[j] = PLEAS_GLOBAL(L.bn_shift)[co];
         } else {
-            // a plain convolution (pleas_conv2d_fwd) has no block maps: every source row is absent, the target is zero
+            // the modes without a target have no block maps: every source row is absent, the target is zero
             ops.row1[j] = L.row1 ? PLEAS_GLOBAL_I(L.row1)[co] : -1;
             ops.row2[j] = L.row2 ? PLEAS_GLOBAL_I(L.row2)[co] : -1;
         }
@@ -108,18 +116,11 @@ __device__ __forceinline__ void fwd_load_maps(const FwdLayerDev& L, const int i0
     }
 }
 
-// PLAIN = 1 (pleas_conv2d_fwd): no target -- nothing is gathered, no loss partial; the epilogue is bias + store
-// PLAIN = 2 (pleas_conv2d_bn_act_fwd): the same, and the activated image  act(fma(y, scale, shift) + identity)  is stored
-// beside y -- the arithmetic of bn_act_kernel (elementwise.hip) on the value that is still in registers; the identity takes
-// the gather slots of the target
-// PLAIN = 3 (pleas_conv2d_act_fwd): PLAIN = 2 without the store of y -- a compile-time mode, so that the kernels of the other
-// modes stay the code they were
-// PLAIN = 4 (pleas_conv2d_bn_stats_fwd): PLAIN = 1, then a statistics pass over the tile while it is still in LDS: per output
-// channel the sums of y and y^2 (fp64, y = the fp32 value that was stored) over the tile's live pixels, split at a batch
-// boundary, in a fixed order and without atomics -- what bn_stats_partial_kernel (bn_train.hip) would read y back for
-template <int TM, int PLAIN = 0>
+// Without a target the epilogue is bias + store and leaves no loss partial; the image modes' identity takes the target's gather
+// slots; the statistics pass sums the fp32 values that were stored, split at a batch boundary.
+template <int TM, FwdMode MODE = FwdMode::Fit>
 __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItemDev& it, f32x16 (&acc)[TM / 64][2],
-                                             const FwdRowOps<TM, PLAIN>& ops, float* smem, float* __restrict__ partials) {
+                                             const FwdRowOps<TM, fwd_has_image(MODE)>& ops, float* smem, float* __restrict__ partials) {
     constexpr int MTM = TM / 64;
     constexpr int ROWS = TM / 8, GB = 8, NB = ROWS / GB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -143,10 +144,10 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
         __syncthreads();
     };
     float sq = 0.f;
-    // PLAIN == 4: the statistics pass gives TM / 256 threads to a channel row; that row's bias is requested here, ahead of the spill
+    // the statistics pass gives TM / 256 threads to a channel row; that row's bias is requested here, ahead of the spill
     constexpr int SPR = kThreads / TM;       // threads per row of the statistics pass
     float st_bias = 0.f;
-    if constexpr (PLAIN == 4) st_bias = L.bias ? PLEAS_GLOBAL(L.bias)[min(i0 + tid / SPR, L.Cout - 1)] : 0.f;
+    if constexpr (fwd_has_stats(MODE)) st_bias = L.bias ? PLEAS_GLOBAL(L.bias)[min(i0 + tid / SPR, L.Cout - 1)] : 0.f;
     const bool vec_ok = (L.HWo % 4 == 0);   // then a 4-pixel group never straddles samples and is 16-B aligned
     const int pg = (tid & 31) * 4;           // pixel group of this thread
     const uint32_t Pg = p0 + pg;
@@ -164,9 +165,9 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
         const uint32_t hw4 = 4u * L.HWo;
         const uint32_t gbase = 4u * (gn * (uint32_t)L.Csrc * L.HWo + gp);
         const uint32_t rbase = 4u * ((gn * (uint32_t)L.Cout + (uint32_t)i0 + (uint32_t)(tid >> 5)) * L.HWo + gp);
-        // PLAIN == 2: the identity (shaped like the output) stands where the first source's outputs are gathered from
-        const bool has_res = fwd_has_image(PLAIN) && L.bn_res != nullptr;
-        const char* o1b = reinterpret_cast<const char*>(fwd_has_image(PLAIN) ? (has_res ? L.bn_res : L.ip) : L.o1);
+        // the image modes: the identity (shaped like the output) stands where the first source's outputs are gathered from
+        const bool has_res = fwd_has_image(MODE) && L.bn_res != nullptr;
+        const char* o1b = reinterpret_cast<const char*>(fwd_has_image(MODE) ? (has_res ? L.bn_res : L.ip) : L.o1);
         const char* o2b = reinterpret_cast<const char*>(L.o2);
         char* rb_ = reinterpret_cast<char*>(L.resid);
         char* zb_ = reinterpret_cast<char*>(L.bn_z);
@@ -174,7 +175,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
 #pragma unroll
             for (int u = 0; u < GB; ++u) {
                 const int j = bt * GB + u;
-                if constexpr (fwd_has_image(PLAIN)) {
+                if constexpr (fwd_has_image(MODE)) {
                     // unconditional load from a valid address (the output's own offset into the identity; the first floats
                     // of the input for rows / pixels outside the layer and when there is no identity -- then voided by a
                     // select): no branch around a load
@@ -182,7 +183,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                     const uint32_t oz = live ? rbase + (uint32_t)(8 * j) * hw4 : 0u;
                     const f32x4 idn = *(const __attribute__((address_space(1))) f32x4*)(o1b + oz);
                     ta[bt][u] = has_res ? idn : f32x4{0.f, 0.f, 0.f, 0.f};
-                } else if constexpr (PLAIN) {
+                } else if constexpr (!fwd_has_target(MODE)) {
                     ta[bt][u] = tb[bt][u] = f32x4{0.f, 0.f, 0.f, 0.f};
                 } else {
                     const uint32_t oa = (gin && ops.row1[j] >= 0) ? gbase + (uint32_t)ops.row1[j] * hw4 : 0u;
@@ -198,7 +199,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const int j = bt * GB + u;
                 const int lco = (tid >> 5) + 8 * j, co = i0 + lco;
                 const bool live = gin && co < L.Cout;
-                if constexpr (fwd_has_image(PLAIN)) {
+                if constexpr (fwd_has_image(MODE)) {
                     const f32x4 o = *reinterpret_cast<const f32x4*>(Ct + lco * EL + pg);
                     f32x4 y, z;
 #pragma unroll
@@ -208,7 +209,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                         z[e] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
                     }
                     if (live) {
-                        if constexpr (PLAIN == 2) *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = y;
+                        if constexpr (fwd_stores_y(MODE)) *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = y;
                         *(__attribute__((address_space(1))) f32x4*)(zb_ + (rbase + (uint32_t)(8 * j) * hw4)) = z;
                     }
                 } else {
@@ -248,11 +249,11 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                 const uint32_t Pe = Pg + e;
                 if (Pe >= L.Ptot) break;
                 const uint32_t n = Pe / L.HWo, p = Pe - n * L.HWo;
-                if constexpr (fwd_has_image(PLAIN)) {
+                if constexpr (fwd_has_image(MODE)) {
                     const size_t at = ((size_t)n * L.Cout + co) * L.HWo + p;
                     const float y = o[e] + ops.bias[j];
                     const float sm = fmaf(y, ops.scale[j], ops.shift[j]) + (L.bn_res ? PLEAS_GLOBAL(L.bn_res)[at] : 0.f);
-                    if constexpr (PLAIN == 2) PLEAS_GLOBAL_W(L.resid)[at] = y;
+                    if constexpr (fwd_stores_y(MODE)) PLEAS_GLOBAL_W(L.resid)[at] = y;
                     PLEAS_GLOBAL_W(L.bn_z)[at] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
                 } else {
                     float a = 0.f, b = 0.f;
@@ -265,7 +266,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
             }
         }
     }
-    if constexpr (PLAIN == 4) {
+    if constexpr (fwd_has_stats(MODE)) {
         // Thread (row r, part q) sums NCH 16-byte groups of its row: q's groups are q * NCH .. + NCH - 1, visited from a start
         // that is rotated per q so that the 16 lanes of a ds_read_b128 group fall on 16 different bank quads (rows are 33 quads
         // apart).  The order is a function of (r, q) alone: the same bits run after run.
@@ -354,7 +355,7 @@ struct FwdWeightRows {
     }
 };
 
-template <int TM, int VECA, int PLAIN = 0>
+template <int TM, int VECA, FwdMode MODE = FwdMode::Fit>
 __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev& it, float* smem, float* __restrict__ partials) {
     constexpr int MTM = TM / 64;
     using WRows = FwdWeightRows<TM, VECA>;
@@ -496,7 +497,7 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
     load_chunk(0);
     store_chunk(0);
     __syncthreads();
-    FwdRowOps<TM, PLAIN> ops;
+    FwdRowOps<TM, fwd_has_image(MODE)> ops;
     for (int c = 0; c + 1 < nchunks; ++c) {
         const int buf = c & 1;
         load_chunk(c + 1);
@@ -504,11 +505,11 @@ __device__ __forceinline__ void fwd_tile(const FwdLayerDev& L, const FwdItemDev&
         store_chunk(buf ^ 1);
         __syncthreads();
     }
-    fwd_load_maps<TM, PLAIN>(L, i0, ops);
+    fwd_load_maps<TM, MODE>(L, i0, ops);
     compute((nchunks - 1) & 1);
     __syncthreads();
 
-    fwd_epilogue<TM, PLAIN>(L, it, acc, ops, smem, partials);
+    fwd_epilogue<TM, MODE>(L, it, acc, ops, smem, partials);
 }
 
 
@@ -540,7 +541,7 @@ constexpr int fFlatColsK = 248;    // columns of that image: 128 + 2 * halo data
 //                 ds_read_b64_tr_b16 -- the hardware transposes 4 k x 16 pixels per 16-lane group
 constexpr int fSplitPixRow = 160;  // bf16 per k row of the 1 x 1 split image: 128 pixels + 32 pad = 320 B (rows 16 banks apart:
                                    // the four rows x eight 8-byte column chunks of a half-wave's transposed read hit 32 distinct bank pairs)
-template <int TM, int KIND, int SPLIT = 0, int PLAIN = 0>
+template <int TM, int KIND, int SPLIT = 0, FwdMode MODE = FwdMode::Fit>
 __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdItemDev& it, float* smem, float* __restrict__ partials) {
     static_assert(!SPLIT || KIND != 1, "the scalar 1 x 1 form (7 x 7 images) has no split variant");
     constexpr int MTM = TM / 64;
@@ -833,7 +834,7 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
     store_a(0, ra0);
     store_b(0, rb0);
     __syncthreads();
-    FwdRowOps<TM, PLAIN> ops;
+    FwdRowOps<TM, fwd_has_image(MODE)> ops;
     // Software pipeline, two chunks deep for the global loads: while chunk c computes, the operands of chunk c + 1 are in
     // flight or in registers (requested one iteration earlier) and those of chunk c + 2 are requested.  k x k forms load
     // the input image of the next channel block two taps before its first use.
@@ -898,10 +899,10 @@ __device__ __forceinline__ void fwd_flat_tile(const FwdLayerDev& L, const FwdIte
         step(c, r, ra1, ra0, rb1, rb0);
         r = ra_;
     }
-    fwd_load_maps<TM, PLAIN>(L, i0, ops);                   // epilogue operands, requested under the last chunk's MFMAs
+    fwd_load_maps<TM, MODE>(L, i0, ops);                    // epilogue operands, requested under the last chunk's MFMAs
     compute((nchunks - 1) & 1, bsel, r);
     __syncthreads();
-    fwd_epilogue<TM, PLAIN>(L, it, acc, ops, smem, partials);
+    fwd_epilogue<TM, MODE>(L, it, acc, ops, smem, partials);
 }
 
 // One kernel per tile form (register allocation and LDS are then per form, not the maximum over all of them); the host
@@ -954,29 +955,30 @@ __global__ __launch_bounds__(kThreads, kFwdForms[FORM].occupancy[SPLIT]) void fw
 }
 // A plain convolution (pleas_conv2d_fwd): ONE layer, described in the kernel arguments; the work item is the block index
 // (output-channel tile fastest, as in the grouped plan), no tables, no target, no loss.
-template <int FORM, int SPLIT = 0, int BN = 0>
+template <int FORM, int SPLIT, FwdMode MODE>
 __global__ __launch_bounds__(kThreads, kFwdForms[FORM].occupancy[SPLIT]) void conv2d_fwd_kernel(const FwdLayerDev L, const int tms) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const FwdItemDev it{0, (int)(blockIdx.x % (unsigned)tms), (int)(blockIdx.x / (unsigned)tms), 0};
     constexpr FwdForm F = kFwdForms[FORM];
-    constexpr int PLAIN = 1 + BN;      // 2: the BatchNorm / add / ReLU image is written beside the output; 3: that image alone;
-                                       // 4: the output and its tile's batch statistics
-    if constexpr (F.flat) fwd_flat_tile<F.tm, F.sub, SPLIT, PLAIN>(L, it, smem, nullptr);
-    else fwd_tile<F.tm, F.sub, PLAIN>(L, it, smem, nullptr);
+    static_assert(!fwd_has_target(MODE), "the fit has its own kernel: tables of layers and items, loss partials");
+    if constexpr (F.flat) fwd_flat_tile<F.tm, F.sub, SPLIT, MODE>(L, it, smem, nullptr);
+    else fwd_tile<F.tm, F.sub, MODE>(L, it, smem, nullptr);
 }
 // The kernels of a form, [arithmetic = pleas_arith's mode]: a form without split kernels keeps its exact one there.
 struct FwdFormKernels {
     void (*batch[3])(const FwdLayerDev*, const FwdItemDev*, float*);
-    void (*conv2d[4][3])(const FwdLayerDev, const int);      // [BN][arithmetic]; BN 2: image only; BN 3: output + batch statistics
+    void (*conv2d[fModes][3])(const FwdLayerDev, const int);      // [FwdMode][arithmetic]; none for Fit (`batch`)
 };
 template <int FORM>
 static constexpr FwdFormKernels fwd_form_kernels() {
     constexpr int S = kFwdForms[FORM].split ? 1 : 0, S9 = kFwdForms[FORM].split ? 2 : 0;
+    using M = FwdMode;
     return {{fwd_batch_kernel<FORM, 0>, fwd_batch_kernel<FORM, S>, fwd_batch_kernel<FORM, S9>},
-            {{conv2d_fwd_kernel<FORM, 0, 0>, conv2d_fwd_kernel<FORM, S, 0>, conv2d_fwd_kernel<FORM, S9, 0>},
-             {conv2d_fwd_kernel<FORM, 0, 1>, conv2d_fwd_kernel<FORM, S, 1>, conv2d_fwd_kernel<FORM, S9, 1>},
-             {conv2d_fwd_kernel<FORM, 0, 2>, conv2d_fwd_kernel<FORM, S, 2>, conv2d_fwd_kernel<FORM, S9, 2>},
-             {conv2d_fwd_kernel<FORM, 0, 3>, conv2d_fwd_kernel<FORM, S, 3>, conv2d_fwd_kernel<FORM, S9, 3>}}};
+            {{nullptr, nullptr, nullptr},
+             {conv2d_fwd_kernel<FORM, 0, M::Conv>, conv2d_fwd_kernel<FORM, S, M::Conv>, conv2d_fwd_kernel<FORM, S9, M::Conv>},
+             {conv2d_fwd_kernel<FORM, 0, M::ConvImage>, conv2d_fwd_kernel<FORM, S, M::ConvImage>, conv2d_fwd_kernel<FORM, S9, M::ConvImage>},
+             {conv2d_fwd_kernel<FORM, 0, M::Image>, conv2d_fwd_kernel<FORM, S, M::Image>, conv2d_fwd_kernel<FORM, S9, M::Image>},
+             {conv2d_fwd_kernel<FORM, 0, M::ConvStats>, conv2d_fwd_kernel<FORM, S, M::ConvStats>, conv2d_fwd_kernel<FORM, S9, M::ConvStats>}}};
 }
 static const FwdFormKernels kFwdKernels[fForms] = {fwd_form_kernels<0>(), fwd_form_kernels<1>(), fwd_form_kernels<2>(), fwd_form_kernels<3>(),
                                                    fwd_form_kernels<4>(), fwd_form_kernels<5>(), fwd_form_kernels<6>(), fwd_form_kernels<7>(),
@@ -1243,64 +1245,77 @@ extern "C" size_t pleas_fwd_batch_ws_bytes(const pleas_fwd_layer* layers, int n_
     return tmp.total;
 }
 
-// y = conv(x, w) (+ bias); with `scale`: also z = act(y * scale[c] + shift[c] (+ res)) in the same epilogue; `image_only`
-// (with `scale`): z alone, y is neither given nor stored; `st_part` (without `scale`): the tiles' batch statistics beside y, st_pb
-// pixels per batch
-static int conv2d_launch(const float* x, const float* w, const float* bias, float* y, const float* scale, const float* shift,
-                         const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH, int KW,
-                         int stride, int pad, int flags, void* stream_, bool image_only = false, double* st_part = nullptr,
-                         uint32_t st_pb = 0) {
-    if (!x || !w || (!y && !image_only)) return bad_arg("conv2d_fwd: null pointer");
-    if (((uintptr_t)w & 15) != 0 || ((uintptr_t)x & 15) != 0) return bad_arg("conv2d_fwd: x and w must be 16-byte aligned");
-    const bool bn = scale != nullptr;
-    if (image_only && (!bn || y)) return bad_arg("conv2d_act_fwd: the image-only epilogue takes scale and no y");
-    if (bn && (!shift || !z)) return bad_arg("conv2d_bn_act_fwd: scale needs shift and z");
-    if (bn && ((((uintptr_t)y | (uintptr_t)z | (uintptr_t)res) & 15) != 0))
+// One plain convolution call: the operands, the geometry, the mode and that mode's operands.
+struct Conv2dCall {
+    FwdMode mode;
+    const float *x, *w, *bias;
+    float* y;                                    // null under Image
+    int N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags;
+    void* stream;
+    const float *scale = nullptr, *shift = nullptr, *res = nullptr;      // the image modes: res may be null
+    float* z = nullptr;
+    int relu = 0;                                // ReLU after the map
+};
+// its description; ConvStats: the caller sets d.st_part / d.st_pb once its own refusals are past
+struct Conv2dPlan { FwdLayerDev d; size_t lds = 0; int TM = 128; };
+
+// Every refusal of a call, and its description; no HIP call.
+static int conv2d_describe(const Conv2dCall& c, Conv2dPlan& p) {
+    FwdLayerDev& d = p.d;
+    if (!c.x || !c.w || (!c.y && fwd_stores_y(c.mode))) return bad_arg("conv2d_fwd: null pointer");
+    if (((uintptr_t)c.w & 15) != 0 || ((uintptr_t)c.x & 15) != 0)
+        return bad_arg(fwd_has_stats(c.mode) ? "conv2d_bn_stats_fwd: x and w must be 16-byte aligned" : "conv2d_fwd: x and w must be 16-byte aligned");
+    if (fwd_has_image(c.mode) && ((((uintptr_t)c.y | (uintptr_t)c.z | (uintptr_t)c.res) & 15) != 0))
         return bad_arg("conv2d_bn_act_fwd: y, z and res must be 16-byte aligned");
-    pleas_fwd_layer l{};
-    l.ip = x; l.w = w; l.bias = bias; l.resid = y;
-    l.N = N; l.Cout = Cout; l.Cin = Cin; l.Hin = Hin; l.Win = Win; l.KH = KH; l.KW = KW; l.stride = stride; l.pad = pad;
-    l.Csrc = 1; l.n_merged = 0; l.dscale = 1.f; l.loss_scale = 0.f; l.flags = flags;
-    FwdLayerDev d{};
-    size_t lds = 0;
-    int TM = 128;
-    if (const int rc = fwd_describe(l, d, lds, TM); rc != PLEAS_OK) return rc;
+    pleas_fwd_layer l{};      // the geometry alone is read
+    l.N = c.N; l.Cout = c.Cout; l.Cin = c.Cin; l.Hin = c.Hin; l.Win = c.Win; l.KH = c.KH; l.KW = c.KW; l.stride = c.stride; l.pad = c.pad;
+    l.Csrc = 1; l.dscale = 1.f; l.flags = c.flags;
+    d = FwdLayerDev{};
+    if (const int rc = fwd_describe(l, d, p.lds, p.TM); rc != PLEAS_OK) return rc;
     // no block maps: every source row is absent (fwd_load_maps), the masked gathers read the first floats of x
-    d.ip = x; d.w = w; d.bias = bias; d.o1 = x; d.o2 = x; d.row1 = nullptr; d.row2 = nullptr; d.resid = y;
-    d.part_base = 0;
-    d.bn_scale = scale; d.bn_shift = shift; d.bn_res = res; d.bn_z = z; d.bn_relu = relu ? 1 : 0;
-    d.st_part = st_part; d.st_pb = st_pb;
-    const int tms = (int)ceil_div(Cout, TM), tps = (int)ceil_div((int64_t)d.Ptot, fTN);
+    d.ip = c.x; d.w = c.w; d.bias = c.bias; d.o1 = c.x; d.o2 = c.x; d.resid = c.y;
+    d.bn_scale = c.scale; d.bn_shift = c.shift; d.bn_res = c.res; d.bn_z = c.z; d.bn_relu = c.relu ? 1 : 0;
+    return PLEAS_OK;
+}
+
+static int conv2d_enqueue(const Conv2dCall& c, const Conv2dPlan& p) {
+    const FwdLayerDev& d = p.d;
+    const int tms = (int)ceil_div(c.Cout, p.TM), tps = (int)ceil_div((int64_t)d.Ptot, fTN);
     const dim3 grid((unsigned)((int64_t)tms * tps));
-    hipStream_t st = (hipStream_t)stream_;
-    const double out_floats = (double)Cout * d.Ptot;
-    ProfScope prof(kProfConv2d, 2.0 * Cout * (double)d.Kd * (double)d.Ptot,
-                   ((double)Cin * N * Hin * Win + out_floats * ((bn && !image_only ? 2.0 : 1.0) + (res ? 1.0 : 0.0))) * sizeof(float), st);
-    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[bn ? (image_only ? 2 : 1) : (st_part ? 3 : 0)][arith_mode()], grid, dim3(kThreads), lds, st,
-                       d, tms);
+    hipStream_t st = (hipStream_t)c.stream;
+    const double out_floats = (double)c.Cout * d.Ptot;
+    ProfScope prof(kProfConv2d, 2.0 * c.Cout * (double)d.Kd * (double)d.Ptot,
+                   ((double)c.Cin * c.N * c.Hin * c.Win + out_floats * ((c.mode == FwdMode::ConvImage ? 2.0 : 1.0) + (c.res ? 1.0 : 0.0))) * sizeof(float), st);
+    hipLaunchKernelGGL(kFwdKernels[fwd_form_of(d.variant)].conv2d[(int)c.mode][arith_mode()], grid, dim3(kThreads), p.lds, st, d, tms);
     PLEAS_LAUNCH_CHECK("conv2d_fwd_kernel");
     return PLEAS_OK;
 }
 
+static int conv2d_launch(const Conv2dCall& c) {
+    Conv2dPlan p;
+    if (const int rc = conv2d_describe(c, p); rc != PLEAS_OK) return rc;
+    return conv2d_enqueue(c, p);
+}
+
 extern "C" int pleas_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Hin, int Win,
                                 int Cout, int KH, int KW, int stride, int pad, int flags, void* stream_) {
-    return conv2d_launch(x, w, bias, y, nullptr, nullptr, nullptr, nullptr, 0, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags,
-                         stream_);
+    return conv2d_launch(Conv2dCall{FwdMode::Conv, x, w, bias, y, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_});
 }
 
 extern "C" int pleas_conv2d_bn_act_fwd(const float* x, const float* w, const float* bias, float* y, const float* scale,
                                        const float* shift, const float* res, float* z, int relu, int N, int Cin, int Hin,
                                        int Win, int Cout, int KH, int KW, int stride, int pad, int flags, void* stream_) {
     if (!scale || !shift || !z) return bad_arg("conv2d_bn_act_fwd: null pointer");
-    return conv2d_launch(x, w, bias, y, scale, shift, res, z, relu, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_);
+    return conv2d_launch(Conv2dCall{FwdMode::ConvImage, x, w, bias, y, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_,
+                                    scale, shift, res, z, relu});
 }
 
 extern "C" int pleas_conv2d_act_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
                                     const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH,
                                     int KW, int stride, int pad, int flags, void* stream_) {
     if (!scale || !shift || !z) return bad_arg("conv2d_act_fwd: null pointer");
-    return conv2d_launch(x, w, bias, nullptr, scale, shift, res, z, relu, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_,
-                         true);
+    return conv2d_launch(Conv2dCall{FwdMode::Image, x, w, bias, nullptr, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_,
+                                    scale, shift, res, z, relu});
 }
 
 // Workspace of pleas_conv2d_bn_stats_fwd, in doubles: what bn_train_finalize_kernel takes with S = 1 -- the sums per (batch,
@@ -1324,14 +1339,10 @@ extern "C" int pleas_conv2d_bn_stats_fwd(const float* x, const float* w, const f
     if (N <= 0 || N % batches != 0) return bad_arg("conv2d_bn_stats_fwd: the samples do not split into the batches");
     if ((running_mean == nullptr) != (running_var == nullptr))
         return bad_arg("conv2d_bn_stats_fwd: running_mean / running_var: both or neither");
-    pleas_fwd_layer l{};
-    l.N = N; l.Cout = Cout; l.Cin = Cin; l.Hin = Hin; l.Win = Win; l.KH = KH; l.KW = KW; l.stride = stride; l.pad = pad;
-    l.Csrc = 1; l.flags = flags;
-    FwdLayerDev d{};
-    size_t lds = 0;
-    int TM = 128;
-    if (const int rc = fwd_describe(l, d, lds, TM); rc != PLEAS_OK) return rc;
-    if (((uintptr_t)w & 15) != 0 || ((uintptr_t)x & 15) != 0) return bad_arg("conv2d_bn_stats_fwd: x and w must be 16-byte aligned");
+    Conv2dCall c{FwdMode::ConvStats, x, w, bias, y, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, flags, stream_};
+    Conv2dPlan p;
+    if (const int rc = conv2d_describe(c, p); rc != PLEAS_OK) return rc;
+    FwdLayerDev& d = p.d;
     const int64_t per_batch = (int64_t)(N / batches) * d.HWo;      // values per channel and batch
     if (per_batch <= 1) return bad_arg("conv2d_bn_stats_fwd: more than one value per channel is needed");
     // a tile has two segments: it may touch two batches, not three
@@ -1341,12 +1352,10 @@ extern "C" int pleas_conv2d_bn_stats_fwd(const float* x, const float* w, const f
     if (!ws || ws_bytes < need) return workspace_too_small("conv2d_bn_stats_fwd", need);
     if ((uintptr_t)ws & 7) return bad_arg("conv2d_bn_stats_fwd: workspace must be 8-byte aligned");
     double* sums = (double*)ws;
-    double* tile_part = sums + conv_bn_stats_head(Cout, batches);
-    if (const int rc = conv2d_launch(x, w, bias, y, nullptr, nullptr, nullptr, nullptr, 0, N, Cin, Hin, Win, Cout, KH, KW, stride, pad,
-                                     flags, stream_, false, tile_part, (uint32_t)per_batch);
-        rc != PLEAS_OK)
-        return rc;
-    return bn_fold_tile_partials(tile_part, fTN, d.Ptot, (uint32_t)per_batch, Cout, batches, sums, gamma, beta, eps, momentum,
+    d.st_part = sums + conv_bn_stats_head(Cout, batches);
+    d.st_pb = (uint32_t)per_batch;
+    if (const int rc = conv2d_enqueue(c, p); rc != PLEAS_OK) return rc;
+    return bn_fold_tile_partials(d.st_part, fTN, d.Ptot, (uint32_t)per_batch, Cout, batches, sums, gamma, beta, eps, momentum,
                                  running_mean, running_var, num_batches_tracked, scale, shift, (hipStream_t)stream_);
 }
 

@@ -531,21 +531,29 @@ def bn_act_tracked(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, re
     return (y_bn, y_sum, y) if relu else (y_bn, y, None)
 
 
+def _bn_pointers(name: str, bn: "torch.nn.BatchNorm2d", device: torch.device, channels: Optional[int] = None) -> tuple:
+    """Addresses of ``bn``'s weight, bias, running mean, running variance and batch counter (None where absent or untracked); the first
+    four must be contiguous fp32 on ``device`` and, with ``channels``, of that length (a merged model's ``num_features`` may be stale)."""
+    track = bn.track_running_stats and bn.running_mean is not None
+    tensors = (bn.weight, bn.bias) + ((bn.running_mean, bn.running_var, bn.num_batches_tracked) if track else (None, None, None))
+    for t in tensors[:4]:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != device
+                              or (channels is not None and t.numel() != channels)):
+            raise PleasHipError("%s: BatchNorm parameters / buffers must be contiguous fp32 %son x's device"
+                                % (name, "" if channels is None else "vectors of %d channels " % channels))
+    return tuple(t.data_ptr() if t is not None else None for t in tensors)
+
+
 def _bn_train_args(bn: "torch.nn.BatchNorm2d", x: torch.Tensor, batches: int = 1):
     """Checks and addresses shared by ``bn_train_fold`` and ``BnTrainFold``: ``(n, C, inner, pointers)`` with ``n`` samples per
-    batch and ``pointers`` = weight, bias, running mean, running variance, batch counter (None where absent or untracked)."""
+    batch and ``pointers`` as ``_bn_pointers`` returns them."""
     if x.shape[0] % batches:
         raise PleasHipError("bn_train_fold: %d samples do not split into %d batches" % (x.shape[0], batches))
     n, C = x.shape[0] // batches, x.shape[1]
     inner = math.prod(x.shape[2:])
     if n * inner <= 1:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
-    track = bn.track_running_stats and bn.running_mean is not None
-    tensors = (bn.weight, bn.bias) + ((bn.running_mean, bn.running_var, bn.num_batches_tracked) if track else (None, None, None))
-    for t in tensors[:4]:
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device):
-            raise PleasHipError("bn_train_fold: BatchNorm parameters / buffers must be contiguous fp32 on x's device")
-    return n, C, inner, tuple(t.data_ptr() if t is not None else None for t in tensors)
+    return n, C, inner, _bn_pointers("bn_train_fold", bn, x.device)
 
 
 def bn_train_fold(bn: "torch.nn.BatchNorm2d", x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -562,23 +570,34 @@ def bn_train_fold(bn: "torch.nn.BatchNorm2d", x: torch.Tensor) -> Tuple[torch.Te
     need = int(lib.pleas_bn_train_ws_bytes(n, C))
     ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
     out = torch.empty(2, C, dtype=torch.float32, device=x.device)
-    rc = lib.pleas_bn_train_fold(x.data_ptr(), n, C, inner, w, b, float(bn.eps),
-                                 -1.0 if bn.momentum is None else float(bn.momentum), rm, rv, nbt,
+    rc = lib.pleas_bn_train_fold(x.data_ptr(), n, C, inner, w, b, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum), rm, rv, nbt,
                                  out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), need, _stream())
     check(rc, "pleas_bn_train_fold")
     return out[0], out[1]
 
 
-class BnTrainFold:
+class _PerModuleFold:
+    """What the per-module train-mode callables share: the module, and what their cached arguments depend on."""
+
+    def __init__(self, bn: "torch.nn.BatchNorm2d"):
+        self.bn = bn
+        self._shape = None
+
+    def _addresses(self) -> tuple:
+        """Compared per call: the addresses of the module's parameters / buffers (``.to()`` swaps ``.data`` under the SAME objects), and the
+        last two arguments they go with: ``eps``, and the momentum (-1: the cumulative average of ``momentum=None``)."""
+        bn = self.bn
+        return tuple(t.data_ptr() if t is not None else 0 for t in
+                     (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)) + (
+                         float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum))
+
+
+class BnTrainFold(_PerModuleFold):
     """``bn_train_fold`` for ONE BatchNorm2d called batch after batch (graph callable of the matching twin in train mode and
     of the BN-reset pass): workspace, output vectors and the module's parameter / buffer addresses are looked up once per
     input shape instead of per call -- those passes are bound by host dispatch (104 BatchNorm2d per ResNet-101 forward).
     The returned ``(scale, shift)`` are views of a buffer that the NEXT call overwrites: consume them on the same stream
     before folding the next batch (what a forward pass does)."""
-
-    def __init__(self, bn: "torch.nn.BatchNorm2d"):
-        self.bn = bn
-        self._shape = None
 
     def _prepare(self, x: torch.Tensor, batches: int) -> None:
         bn = self.bn
@@ -586,17 +605,10 @@ class BnTrainFold:
         need = batches * int(_lib.lib().pleas_bn_train_ws_bytes(n, C))
         self._ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
         self._out = torch.empty(2, batches, C, dtype=torch.float32, device=x.device)
-        self._tensors = self._addresses()      # compared per call: Module._apply swaps .data under the same objects
-        self._args = (n, batches, C, inner, w, b, float(bn.eps), rm, rv, nbt,
+        self._tensors = self._addresses()
+        self._args = (n, batches, C, inner, w, b) + self._tensors[-2:] + (rm, rv, nbt,
                       self._out[0].data_ptr(), self._out[1].data_ptr(), self._ws.data_ptr(), need)
         self._shape = (tuple(x.shape), x.device, batches)
-
-    def _addresses(self) -> tuple:
-        """What the cached arguments depend on: the addresses of the module's parameters / buffers (``.to()`` / ``.float()``
-        swap ``.data`` under the SAME Parameter objects) and ``eps``."""
-        bn = self.bn
-        return tuple(t.data_ptr() if t is not None else 0 for t in
-                     (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)) + (float(bn.eps),)
 
     def __call__(self, x: torch.Tensor, batches: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         """``batches`` > 1: ``x`` is that many batches back to back along dim 0; each is folded on its own samples, in
@@ -604,13 +616,9 @@ class BnTrainFold:
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2:
             raise PleasHipError("bn_train_fold needs an fp32 [N, C, ...] tensor on the GPU")
         x = x.contiguous()
-        bn = self.bn
         if self._shape != (tuple(x.shape), x.device, batches) or self._tensors != self._addresses():
             self._prepare(x, batches)
-        n, nb, C, inner, w, b, eps, rm, rv, nbt, o0, o1, ws, need = self._args
-        rc = _lib.lib().pleas_bn_train_fold_batches(x.data_ptr(), n, nb, C, inner, w, b, eps,
-                                                    -1.0 if bn.momentum is None else float(bn.momentum), rm, rv, nbt, o0, o1,
-                                                    ws, need, _stream())
+        rc = _lib.lib().pleas_bn_train_fold_batches(x.data_ptr(), *self._args, _stream())
         check(rc, "pleas_bn_train_fold_batches")
         return (self._out[0, 0], self._out[1, 0]) if batches == 1 else (self._out[0], self._out[1])
 
@@ -802,15 +810,30 @@ class FwdBatch(_GroupedLaunch):
         self._flush(loss)
 
 
-def _conv_geometry(name: str, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, kpos_major: bool):
-    """``(N, Cin, H, W, Cout, KH, KW, Ho, Wo)`` of a dense square convolution of contiguous 4-D tensors."""
+def _conv_call(name: str, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int, kpos_major: bool, *also):
+    """The argument runs every ``pleas_conv2d_*`` entry point takes for a dense square convolution of contiguous tensors (fp32 on the GPU, as
+    ``also`` must be): ``(x, w, bias addresses)``, ``(N, Cin, H, W, Cout, KH, KW, stride, pad, flags)``, the output's shape ``(N, Cout, Ho, Wo)``."""
+    _need_gpu(x, w, *also)
     if x.dim() != 4 or w.dim() != 4 or not x.is_contiguous() or not w.is_contiguous():
         raise PleasHipError("%s: contiguous 4-D tensors expected" % name)
     N, Cin, H, W = x.shape
     KH, KW = (w.shape[1], w.shape[2]) if kpos_major else (w.shape[2], w.shape[3])
     if (w.shape[3] if kpos_major else w.shape[1]) != Cin:
         raise PleasHipError("%s: %d input channels vs a weight of %s" % (name, Cin, tuple(w.shape)))
-    return N, Cin, H, W, w.shape[0], KH, KW, (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    return ((x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None),
+            (N, Cin, H, W, w.shape[0], KH, KW, stride, pad, FwdBatch.KPOS_MAJOR if kpos_major else 0),
+            (N, w.shape[0], (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1))
+
+
+def _image_operands(name: str, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor], out_shape):
+    """Addresses of the image operands: contiguous scale / shift (fp32 on the GPU: ``_conv_call``) of ``Cout`` elements, an identity like z."""
+    Cout = out_shape[1]
+    if scale.numel() != Cout or shift.numel() != Cout or not scale.is_contiguous() or not shift.is_contiguous():
+        raise PleasHipError("%s: scale / shift must be contiguous fp32 vectors of %d channels" % (name, Cout))
+    if res is not None and (tuple(res.shape) != out_shape or res.dtype != torch.float32 or not res.is_contiguous()
+                            or res.device != x.device):
+        raise PleasHipError("%s: the identity must be a contiguous fp32 tensor shaped like the output" % name)
+    return scale.data_ptr(), shift.data_ptr(), res.data_ptr() if res is not None else None
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int, kpos_major: bool = False,
@@ -819,13 +842,10 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], strid
     (``pleas_conv2d_fwd``): fp32 MFMA, a fixed summation order -- the same bits run after run, which MIOpen's 3 x 3
     kernels are not (they split K with atomics on small images / batches; tools/r05/probe_conv_classes.py).
     ``kpos_major``: ``w`` is ``[Cout][KH][KW][Cin]`` (needs Cin % 32 == 0; the flat-shift forms of stride-1 layers)."""
-    _need_gpu(x, w)
-    N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d", x, w, stride, pad, kpos_major)
+    operands, geometry, out_shape = _conv_call("conv2d", x, w, bias, stride, pad, kpos_major)
     if out is None:
-        out = torch.empty((N, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    check(_lib.lib().pleas_conv2d_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
-                                      N, Cin, H, W, Cout, KH, KW, stride, pad, FwdBatch.KPOS_MAJOR if kpos_major else 0,
-                                      _stream()), "pleas_conv2d_fwd")
+        out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    check(_lib.lib().pleas_conv2d_fwd(*operands, out.data_ptr(), *geometry, _stream()), "pleas_conv2d_fwd")
     return out
 
 
@@ -911,20 +931,12 @@ def conv2d_bn_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
                   scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor], relu: bool):
     """``y = conv2d(x, w, bias)`` and ``z = bn_act(y, scale, shift, res, relu)`` from ONE launch (``pleas_conv2d_bn_act_fwd``):
     the activated image is written from the registers that hold y, bit for bit what ``bn_act`` makes of y.  Returns ``(y, z)``."""
-    _need_gpu(x, w, scale, shift)
-    N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d_bn_act", x, w, stride, pad, kpos_major)
-    if scale.numel() != Cout or shift.numel() != Cout or scale.dtype != torch.float32 or shift.dtype != torch.float32:
-        raise PleasHipError("conv2d_bn_act: scale / shift must be fp32 vectors of %d channels" % Cout)
-    if res is not None and (tuple(res.shape) != (N, Cout, Ho, Wo) or res.dtype != torch.float32 or not res.is_contiguous()
-                            or res.device != x.device):
-        raise PleasHipError("conv2d_bn_act: the identity must be a contiguous fp32 tensor shaped like the output")
-    y = torch.empty((N, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    operands, geometry, out_shape = _conv_call("conv2d_bn_act", x, w, bias, stride, pad, kpos_major, scale, shift)
+    image = _image_operands("conv2d_bn_act", x, scale, shift, res, out_shape)
+    y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
     z = torch.empty_like(y)
-    check(_lib.lib().pleas_conv2d_bn_act_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                             y.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                             res.data_ptr() if res is not None else None, z.data_ptr(), 1 if relu else 0,
-                                             N, Cin, H, W, Cout, KH, KW, stride, pad,
-                                             FwdBatch.KPOS_MAJOR if kpos_major else 0, _stream()), "pleas_conv2d_bn_act_fwd")
+    check(_lib.lib().pleas_conv2d_bn_act_fwd(*operands, y.data_ptr(), *image, z.data_ptr(), 1 if relu else 0, *geometry, _stream()),
+          "pleas_conv2d_bn_act_fwd")
     return y, z
 
 
@@ -961,14 +973,10 @@ def conv2d_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], s
     bit the ``z`` of ``conv2d_bn_act``, the convolution's own output is never written.  For forwards nobody hooks (evaluation).
     A batch whose output crosses the per-call limit of the kernels is split along the sample axis (``conv2d_sample_split``)
     into calls that write one ``z``.  ``_limit``: the output-element limit, for tests."""
-    _need_gpu(x, w, scale, shift)
-    N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d_act", x, w, stride, pad, kpos_major)
-    if scale.numel() != Cout or shift.numel() != Cout or not scale.is_contiguous() or not shift.is_contiguous():
-        raise PleasHipError("conv2d_act: scale / shift must be contiguous fp32 vectors of %d channels" % Cout)
-    if res is not None and (tuple(res.shape) != (N, Cout, Ho, Wo) or res.dtype != torch.float32 or not res.is_contiguous()
-                            or res.device != x.device):
-        raise PleasHipError("conv2d_act: the identity must be a contiguous fp32 tensor shaped like the output")
-    z = torch.empty((N, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    (_, wp, bp), geometry, out_shape = _conv_call("conv2d_act", x, w, bias, stride, pad, kpos_major, scale, shift)
+    sp, tp, _ = _image_operands("conv2d_act", x, scale, shift, res, out_shape)
+    (N, Cin, H, W), (_, Cout, Ho, Wo) = geometry[:4], out_shape
+    z = torch.empty(out_shape, dtype=torch.float32, device=x.device)
     if N == 0 or Ho <= 0 or Wo <= 0:
         return z
     per_out, per_in = Cout * Ho * Wo, Cin * H * W
@@ -978,11 +986,10 @@ def conv2d_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], s
         # slices of x, z and the identity must start 16-byte aligned: whole groups of `align` samples
         align = max(4 // math.gcd(4, per_out), 4 // math.gcd(4, per_in))
         parts = conv2d_sample_split(N, per_out, Ho * Wo, _limit, align)
-    fn, flags, st = _lib.lib().pleas_conv2d_act_fwd, FwdBatch.KPOS_MAJOR if kpos_major else 0, _stream()
+    fn, st = _lib.lib().pleas_conv2d_act_fwd, _stream()
     for at, n in parts:
-        check(fn(x[at:at + n].data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, scale.data_ptr(),
-                 shift.data_ptr(), res[at:at + n].data_ptr() if res is not None else None, z[at:at + n].data_ptr(),
-                 1 if relu else 0, n, Cin, H, W, Cout, KH, KW, stride, pad, flags, st), "pleas_conv2d_act_fwd")
+        check(fn(x[at:at + n].data_ptr(), wp, bp, sp, tp, res[at:at + n].data_ptr() if res is not None else None,
+                 z[at:at + n].data_ptr(), 1 if relu else 0, n, *geometry[1:], st), "pleas_conv2d_act_fwd")
     return z
 
 
@@ -1001,42 +1008,27 @@ def conv2d_bn_stats_takes(N: int, Cout: int, Ho: int, Wo: int, batches: int) -> 
     return "straddle" if batches > 1 and per_batch < CONV_BN_STATS_TILE else "fused"
 
 
-class ConvBnStats:
+class ConvBnStats(_PerModuleFold):
     """``conv2d`` + ``BnTrainFold`` as ONE call of ``pleas_conv2d_bn_stats_fwd`` for one train-mode BatchNorm2d called forward after
     forward (graph callable of the BN-reset pass): the convolution's work items leave the sums of their tile's outputs, so ``y`` is
     not read back for its statistics.  Workspace, the ``[2][batches][C]`` outputs and the module's addresses are looked up once per
     input shape; ``bn.momentum`` is read per call.  The returned ``(scale, shift)`` are views of a buffer that the NEXT call
     overwrites (as ``BnTrainFold``'s); ``y`` is a fresh tensor."""
 
-    def __init__(self, bn: "torch.nn.BatchNorm2d"):
-        self.bn = bn
-        self._shape = None
-
-    def _addresses(self) -> tuple:
-        return BnTrainFold._addresses(self)
-
     def _prepare(self, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, kpos_major: bool, batches: int) -> None:
         bn = self.bn
-        N, Cin, H, W, Cout, KH, KW, Ho, Wo = _conv_geometry("conv2d_bn_stats", x, w, stride, pad, kpos_major)
+        _, geometry, (N, Cout, Ho, Wo) = _conv_call("conv2d_bn_stats", x, w, None, stride, pad, kpos_major)
         if N % batches:
             raise PleasHipError("conv2d_bn_stats: %d samples do not split into %d batches" % (N, batches))
         if N // batches * max(Ho, 0) * max(Wo, 0) <= 1:
             raise ValueError("Expected more than 1 value per channel when training, got input size %s" % ((N // batches, Cout, Ho, Wo),))
-        track = bn.track_running_stats and bn.running_mean is not None
-        tensors = (bn.weight, bn.bias) + ((bn.running_mean, bn.running_var, bn.num_batches_tracked) if track else (None, None, None))
-        for t in tensors[:4]:
-            # (the tensors' own length: a merged model's modules keep the `num_features` they were built with)
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device or t.numel() != Cout):
-                raise PleasHipError("conv2d_bn_stats: BatchNorm parameters / buffers must be contiguous fp32 vectors of %d "
-                                    "channels on x's device" % Cout)
-        g, b, rm, rv, nbt = (t.data_ptr() if t is not None else None for t in tensors)
+        g, b, rm, rv, nbt = _bn_pointers("conv2d_bn_stats", bn, x.device, Cout)
         need = int(_lib.lib().pleas_conv2d_bn_stats_ws_bytes(N, Cout, Ho, Wo, batches))
         self._ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
         self._out = torch.empty(2, batches, Cout, dtype=torch.float32, device=x.device)
         self._tensors = self._addresses()
-        self._geo = (N, Cin, H, W, Cout, KH, KW, stride, pad, FwdBatch.KPOS_MAJOR if kpos_major else 0, batches)
-        self._bn_args = (g, b, float(bn.eps))
-        self._tail = (rm, rv, nbt, self._out[0].data_ptr(), self._out[1].data_ptr(), self._ws.data_ptr(), need)
+        self._geo = geometry + (batches,)
+        self._tail = (g, b) + self._tensors[-2:] + (rm, rv, nbt, self._out[0].data_ptr(), self._out[1].data_ptr(), self._ws.data_ptr(), need)
         self._y_shape = (N, Cout, Ho, Wo)
         self._shape = (tuple(x.shape), tuple(w.shape), x.device, stride, pad, kpos_major, batches)
 
@@ -1047,12 +1039,9 @@ class ConvBnStats:
         _need_gpu(x, w)
         if self._shape != (tuple(x.shape), tuple(w.shape), x.device, stride, pad, kpos_major, batches) or self._tensors != self._addresses():
             self._prepare(x, w, stride, pad, kpos_major, batches)
-        bn = self.bn
         y = torch.empty(self._y_shape, dtype=torch.float32, device=x.device)
-        g, b, eps = self._bn_args
         rc = _lib.lib().pleas_conv2d_bn_stats_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                  y.data_ptr(), *self._geo, g, b, eps,
-                                                  -1.0 if bn.momentum is None else float(bn.momentum), *self._tail, _stream())
+                                                  y.data_ptr(), *self._geo, *self._tail, _stream())
         check(rc, "pleas_conv2d_bn_stats_fwd")
         return (y, self._out[0, 0], self._out[1, 0]) if batches == 1 else (y, self._out[0], self._out[1])
 

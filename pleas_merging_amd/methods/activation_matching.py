@@ -103,6 +103,8 @@ class _SideStream:
     Side-stream tensors are consumed on the caller's stream and re-used by the side stream only after the
     next ``fork`` (which waits for everything enqueued on the caller's stream) -- no record_stream needed."""
 
+    parts = 1      # batches per forwarded tensor, set around a forward; read by the twin's train-mode BatchNorm folds
+
     def __init__(self, device: torch.device):
         self.side = hip_ops.role_stream(device, "model2")
         self.main = None
@@ -190,52 +192,26 @@ def _bn_chains(traced: _Trace, model1: nn.Module, model2: nn.Module):
     ``{last node of the chain: (bn, add or None, relu or None, residual operand or None)}`` and the set of nodes that are
     produced by the chain's single fused launch instead of their own.  The BatchNorm may be in eval mode (constants
     folded once) or in train mode (batch statistics folded per batch, ``hip_ops.bn_train_fold``), per model."""
-    from .source_forward import _foldable, _foldable_train, _is_add, _is_relu
+    from .source_forward import _foldable, _foldable_train, bn_chain
 
-    mods1, mods2 = dict(model1.named_modules()), dict(model2.named_modules())
-    fx_mods = dict(traced.named_modules())
+    mods1, mods2 = dict(model1.named_modules()), dict(model2.named_modules())      # mods1: the traced model's own
     at, absorbed, claimed = {}, set(), set()
     for node in traced.graph.nodes:
-        if node.op != "call_module" or len(node.args) != 1 or node.kwargs:
+        if (node.op != "call_module" or len(node.args) != 1 or node.kwargs
+                or not all(_foldable(m) or _foldable_train(m) for m in (mods1.get(node.target), mods2.get(node.target)))):
             continue
-        if not all(_foldable(m) or _foldable_train(m) for m in (mods1.get(node.target), mods2.get(node.target))):
-            continue
-        add = relu = res = None
-        users = list(node.users)
-        if len(users) == 1 and _is_relu(users[0], fx_mods):
-            relu = users[0]
-        elif len(users) == 1 and _is_add(users[0]) and users[0] not in claimed and users[0].args[0] is not users[0].args[1]:
-            add = users[0]
-            claimed.add(add)
-            res = add.args[1] if add.args[0] is node else add.args[0]
-            after = list(add.users)
-            if len(after) == 1 and _is_relu(after[0], fx_mods):
-                relu = after[0]
+        add, relu, res = bn_chain(node, mods1, bare_add=True, claimed=claimed)
         last = relu or add or node
         at[last] = (node, add, relu, res)
         absorbed |= {n for n in (node, add, relu) if n is not None and n is not last}
     return at, absorbed
 
 
-def _train_fold(mod: nn.BatchNorm2d, side: int, name: str, streams=None) -> Callable:
-    """Graph callable of a train-mode BatchNorm: ``x -> (scale, shift)`` of THIS batch (and the module's running
-    statistics move on, as in the module's own forward).  When the forward carries several batches back to back
-    (``streams.parts`` > 1) every batch is folded on its own samples, in order, by the same launch: ``[parts, C]`` maps."""
-    folder = hip_ops.BnTrainFold(mod)     # workspace / output vectors / addresses looked up once per input shape
-
-    def fold(x):
-        return folder(x, getattr(streams, "parts", 1))
-
-    fold.__name__ = fold.__qualname__ = "bn_train_fold_%d_%s" % (side, name)
-    return fold
-
-
 def _build_split_twin(model1: nn.Module, model2: nn.Module, axes: Iterable[Axis], emit: Callable, streams: _SideStream,
                       fuse_bn: bool = False, emit_derived: Optional[Callable] = None):
     import operator
 
-    from .. import hip_ops
-    from .source_forward import _foldable, fold_bn
+    from .source_forward import _foldable, _train_fold, fold_bn
 
     traced = _Trace(model1)
     submods = dict(traced.named_modules())
@@ -288,7 +264,7 @@ def _build_split_twin(model1: nn.Module, model2: nn.Module, axes: Iterable[Axis]
                         root.register_buffer(nm_, buf, persistent=False)
                     attrs = (_node(twin, "get_attr", names[0], (), "bn_scale"), _node(twin, "get_attr", names[1], (), "bn_shift"))
                 else:                       # train mode (the reference drivers' mode): this batch's statistics, one pass
-                    fold = _node(twin, "call_function", _train_fold(mod, side, bn.name, streams), (env[side][bn.args[0]],), "bn_stats")
+                    fold = _node(twin, "call_function", _train_fold(mod, "%d_%s" % (side, bn.name), streams), (env[side][bn.args[0]],), "bn_stats")
                     attrs = (_node(twin, "call_function", operator.getitem, (fold, 0), "bn_scale"),
                              _node(twin, "call_function", operator.getitem, (fold, 1), "bn_shift"))
                 fold_attrs[side][bn] = attrs

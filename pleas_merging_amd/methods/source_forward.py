@@ -68,6 +68,25 @@ def own_conv_ok(mod: nn.Module, mode: Optional[str] = None) -> bool:
     return mod.weight.dtype == torch.float32 and k * k <= 64 and (k > 1 or mode == "all")
 
 
+def _own_input(x, w, dims: int = 4):
+    """``x``, made contiguous, when the library's own kernel takes this call -- a CUDA fp32 tensor of ``dims`` dimensions, the weight on
+    the GPU, no autograd; None otherwise (the caller then runs the module)."""
+    if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != dims or not w.is_cuda
+            or (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
+        return None
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def _fire_hooks(mod: nn.Module, x, y):
+    """``mod``'s forward hooks, called as its own ``__call__`` would: ``(the output they leave, did one of them return it)``."""
+    replaced = False
+    for hook in list(mod._forward_hooks.values()):
+        out = hook(mod, (x,), y)
+        if out is not None:
+            y, replaced = out, True
+    return y, replaced
+
+
 class HipConv:
     """Graph callable standing in for a frozen ``nn.Conv2d``: ``hip_ops.conv2d`` on CUDA fp32 inputs without autograd, the
     module itself otherwise.  ``fire_hooks``: the module's forward hooks are called as its own ``__call__`` would (the
@@ -92,15 +111,12 @@ class HipConv:
 
     def __call__(self, x):
         conv = self.conv
-        if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not conv.weight.is_cuda
-                or (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad))):
+        xc = _own_input(x, conv.weight)
+        if xc is None:
             return conv(x)                      # the module's own path, hooks included
-        y = hip_ops.conv2d(x if x.is_contiguous() else x.contiguous(), self.weight(), conv.bias, self.stride, self.pad, self.kpos)
+        y = hip_ops.conv2d(xc, self.weight(), conv.bias, self.stride, self.pad, self.kpos)
         if self.fire_hooks and conv._forward_hooks:
-            for hook in list(conv._forward_hooks.values()):
-                out = hook(conv, (x,), y)
-                if out is not None:
-                    y = out
+            y, _ = _fire_hooks(conv, x, y)
         return y
 
 
@@ -115,28 +131,29 @@ class HipConvBnAct:
     autograd, an identity that is a strided view) goes through the two calls it replaces, as does the activation after a
     hook that RETURNS another output."""
 
+    suffix = "_bn_act"
+
     def __init__(self, own: HipConv):
         self.own = own
-        self.__name__ = self.__qualname__ = own.__name__ + "_bn_act"
+        self.__name__ = self.__qualname__ = own.__name__ + self.suffix
 
-    def _fused_ok(self, x, scale, res) -> bool:
-        conv = self.own.conv
-        return not (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not conv.weight.is_cuda or scale.dim() != 1
-                    or (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad))
-                    or (res is not None and (not res.is_contiguous() or res.dtype != torch.float32 or res.data_ptr() % 16)))
+    def _fused_input(self, x, scale, res):
+        """``x`` for the fused kernel (``_own_input``), or None when it does not take the call."""
+        if scale.dim() != 1 or (res is not None and (not res.is_contiguous() or res.dtype != torch.float32 or res.data_ptr() % 16)):
+            return None
+        return _own_input(x, self.own.conv.weight)
 
     def __call__(self, x, scale, shift, res, relu):
         own, conv = self.own, self.own.conv
-        if not self._fused_ok(x, scale, res):
+        xc = self._fused_input(x, scale, res)
+        if xc is None:
             return _bn_act(own(x), scale, shift, res, relu)
-        y, z = hip_ops.conv2d_bn_act(x if x.is_contiguous() else x.contiguous(), own.weight(), conv.bias, own.stride, own.pad,
-                                     own.kpos, scale, shift, res, relu)
+        y, z = hip_ops.conv2d_bn_act(xc, own.weight(), conv.bias, own.stride, own.pad, own.kpos, scale, shift, res, relu)
         if own.fire_hooks and conv._forward_hooks:
-            for hook in list(conv._forward_hooks.values()):
-                out = hook(conv, (x,), y)
-                if out is not None:
-                    y, z = out, None
-        return z if z is not None else _bn_act(y, scale, shift, res, relu)
+            y, replaced = _fire_hooks(conv, x, y)
+            if replaced:
+                return _bn_act(y, scale, shift, res, relu)
+        return z
 
 
 class HipConvAct(HipConvBnAct):
@@ -144,16 +161,14 @@ class HipConvAct(HipConvBnAct):
     activated image and nothing else.  A convolution that carries forward hooks AT CALL TIME still owes them its output:
     that call takes the two-output path of the parent class, as does everything the fused kernel does not take."""
 
-    def __init__(self, own: HipConv):
-        super().__init__(own)
-        self.__name__ = self.__qualname__ = own.__name__ + "_act"
+    suffix = "_act"
 
     def __call__(self, x, scale, shift, res, relu):
         own, conv = self.own, self.own.conv
-        if (own.fire_hooks and conv._forward_hooks) or not self._fused_ok(x, scale, res):
+        xc = None if own.fire_hooks and conv._forward_hooks else self._fused_input(x, scale, res)
+        if xc is None:
             return super().__call__(x, scale, shift, res, relu)
-        return hip_ops.conv2d_act(x if x.is_contiguous() else x.contiguous(), own.weight(), conv.bias, own.stride, own.pad,
-                                  own.kpos, scale, shift, res, relu)
+        return hip_ops.conv2d_act(xc, own.weight(), conv.bias, own.stride, own.pad, own.kpos, scale, shift, res, relu)
 
 
 class PoolGather:
@@ -182,13 +197,9 @@ class HipLinear:
         self.__name__ = self.__qualname__ = "hip_linear_%s" % tag
 
     def __call__(self, x):
-        fc = self.fc
-        w = fc.weight
-        if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or not w.is_cuda or w.dtype != torch.float32
-                or not w.is_contiguous() or w.data_ptr() % 16
-                or (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
-            return fc(x)
-        return hip_ops.linear(x, w.detach(), fc.bias)
+        fc, w = self.fc, self.fc.weight
+        xc = _own_input(x, w, 2) if w.dtype == torch.float32 and w.is_contiguous() and not w.data_ptr() % 16 else None
+        return fc(x) if xc is None else hip_ops.linear(xc, w.detach(), fc.bias)
 
 
 def _is_global_avgpool(node: torch.fx.Node, mods) -> bool:
@@ -292,13 +303,9 @@ def _is_relu(node: torch.fx.Node, mods) -> bool:
 
 
 def _is_add(node: torch.fx.Node) -> bool:
-    if node.kwargs:
-        return False
-    if node.op == "call_function" and node.target in (operator.add, operator.iadd, torch.add):
-        return len(node.args) == 2 and all(isinstance(a, torch.fx.Node) for a in node.args)
-    if node.op == "call_method" and node.target in ("add", "add_"):
-        return len(node.args) == 2 and all(isinstance(a, torch.fx.Node) for a in node.args)
-    return False
+    named = ((node.op == "call_function" and node.target in (operator.add, operator.iadd, torch.add))
+             or (node.op == "call_method" and node.target in ("add", "add_")))
+    return named and not node.kwargs and len(node.args) == 2 and all(isinstance(a, torch.fx.Node) for a in node.args)
 
 
 def _foldable(bn: nn.Module) -> bool:
@@ -326,11 +333,11 @@ def fold_bn(bn: nn.BatchNorm2d):
     return scale64.float().contiguous(), shift64.float().contiguous()
 
 
-def _train_fold(bn: nn.BatchNorm2d, tag: str, state: Optional[BatchesPerForward] = None) -> Callable:
+def _train_fold(bn: nn.BatchNorm2d, tag: str, state=None) -> Callable:
     """Graph callable of a train-mode BatchNorm: ``x -> (scale, shift)`` of THIS batch; the module's running statistics
     and batch counter move on exactly as in the module's own forward (``hip_ops.bn_train_fold``: one streaming pass).
-    ``state.parts`` > 1: the tensor holds that many batches back to back, each folded on its own samples, in order, by
-    the same launch (``[parts, C]`` maps)."""
+    ``state`` (an object with ``parts``, or None), ``parts`` > 1: the tensor holds that many batches back to back, each folded on
+    its own samples, in order, by the same launch (``[parts, C]`` maps)."""
     folder = hip_ops.BnTrainFold(bn)      # workspace / output vectors / addresses looked up once per input shape
 
     def fold(x):
@@ -361,12 +368,10 @@ class HipConvBnStats:
         self.taken = {"fused": 0, "two_launch": 0, "module": 0}
         self.__name__ = self.__qualname__ = "hip_conv_%s_bn_stats" % tag
 
-    def _path(self, x, parts: int) -> str:
+    def _path(self, shape, parts: int) -> str:
+        """Of a call the own kernels take (``_own_input``), by the input's shape: "fused", "two_launch", or "module" over the limits."""
         own, conv = self.own, self.own.conv
-        if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not conv.weight.is_cuda
-                or (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad))):
-            return "module"
-        N, _, H, W = x.shape
+        N, _, H, W = shape
         Ho, Wo = (H + 2 * own.pad - own.k) // own.stride + 1, (W + 2 * own.pad - own.k) // own.stride + 1
         takes = hip_ops.conv2d_bn_stats_takes(N, conv.weight.shape[0], Ho, Wo, parts)
         if takes == "limits":
@@ -376,12 +381,13 @@ class HipConvBnStats:
     def __call__(self, x):
         own, conv = self.own, self.own.conv
         parts = self.state.parts if self.state is not None else 1
-        path = self._path(x, parts)
+        xc = _own_input(x, conv.weight)
+        path = "module" if xc is None else self._path(xc.shape, parts)
         self.taken[path] += 1
         if path != "fused":
             y = conv(x) if path == "module" else own(x)
             return (y,) + tuple(self.folder(y, parts))
-        return self.fused(x if x.is_contiguous() else x.contiguous(), own.weight(), conv.bias, own.stride, own.pad, own.kpos, parts)
+        return self.fused(xc, own.weight(), conv.bias, own.stride, own.pad, own.kpos, parts)
 
 
 def _own_convs(graph: torch.fx.Graph, mods, conv: Optional[str]) -> int:
@@ -425,6 +431,104 @@ def _conv_stats_pairs(graph: torch.fx.Graph, op: Callable, pool_op: Optional[Cal
         graph.erase_node(src)
 
 
+def bn_chain(node: torch.fx.Node, mods, bare_add: bool, claimed: Optional[set] = None):
+    """``(add, relu, residual)`` of the chain ``node -> [+ other] -> [ReLU]`` behind BatchNorm call ``node`` whose links have no
+    other consumer (None where absent); ``x + x`` is no residual add.  ``bare_add``: an add that no sole ReLU follows is taken too
+    (else the BatchNorm stands alone).  ``claimed``: the adds taken so far -- none is taken twice, the one taken here joins them."""
+    users = list(node.users)
+    if len(users) != 1:
+        return None, None, None
+    if _is_relu(users[0], mods):
+        return None, users[0], None
+    add = users[0]
+    if not _is_add(add) or add.args[0] is add.args[1] or (claimed is not None and add in claimed):
+        return None, None, None
+    after = list(add.users)
+    relu = after[0] if len(after) == 1 and _is_relu(after[0], mods) else None
+    if relu is None and not bare_add:
+        return None, None, None
+    if claimed is not None:
+        claimed.add(add)
+    return add, relu, add.args[1] if add.args[0] is node else add.args[0]
+
+
+def _fold_chains(graph: torch.fx.Graph, mods, op: Callable, pool_op: Optional[Callable], train_stats: bool,
+                 state: BatchesPerForward, constants: dict) -> int:
+    """Every foldable BatchNorm2d call with its chain (``bn_chain``; an add only before a sole ReLU; a max pooling behind
+    BN -> ReLU for ``pool_op``) becomes one ``op`` / ``pool_op`` call; eval-mode maps go to ``constants``.  Returns how many."""
+    folded = 0
+    for node in list(graph.nodes):
+        if node.op != "call_module" or len(node.args) != 1 or node.kwargs:
+            continue
+        bn = mods.get(node.target)
+        per_batch = train_stats and _foldable_train(bn)
+        if not (per_batch or _foldable(bn)):
+            continue
+        tag = node.name
+        if not per_batch:
+            constants["_pleas_scale_%s" % tag], constants["_pleas_shift_%s" % tag] = fold_bn(bn)
+        add, relu, res = bn_chain(node, mods, bare_add=False)
+        pool = next(iter(relu.users)) if pool_op is not None and relu is not None and res is None and len(relu.users) == 1 else None
+        window = _pool_window(pool, mods) if pool is not None else None
+        chain = [n for n in (node, add, relu, pool if window is not None else None) if n is not None]
+        last = chain[-1]
+        with graph.inserting_before(last):
+            # explicit base names: fx would otherwise derive them from the targets character by character
+            if per_batch:
+                stats = graph.create_node("call_function", _train_fold(bn, tag, state), (node.args[0],), {}, name="bn_stats")
+                s = graph.create_node("call_function", operator.getitem, (stats, 0), {}, name="bn_scale")
+                t = graph.create_node("call_function", operator.getitem, (stats, 1), {}, name="bn_shift")
+            else:
+                s = graph.create_node("get_attr", "_pleas_scale_%s" % tag, (), {}, name="bn_scale")
+                t = graph.create_node("get_attr", "_pleas_shift_%s" % tag, (), {}, name="bn_shift")
+            if window is not None:
+                fused = graph.create_node("call_function", pool_op, (node.args[0], s, t) + window + (True,), {}, name="bn_act_pool")
+            else:
+                fused = graph.create_node("call_function", op, (node.args[0], s, t, res, relu is not None), {}, name="bn_act")
+        last.replace_all_uses_with(fused)
+        for dead in reversed(chain):
+            graph.erase_node(dead)
+        folded += 1
+    return folded
+
+
+def _conv_chain_pairs(graph: torch.fx.Graph, op: Callable) -> None:
+    """An own convolution consumed by one eval-mode chain only (constants, not per-batch statistics): ONE ``HipConvBnAct`` call."""
+    for node in list(graph.nodes):
+        if not (node.op == "call_function" and node.target is op and isinstance(node.args[0], torch.fx.Node)):
+            continue
+        src, s = node.args[0], node.args[1]
+        if not (src.op == "call_function" and isinstance(src.target, HipConv) and len(src.users) == 1
+                and isinstance(s, torch.fx.Node) and s.op == "get_attr"):
+            continue
+        with graph.inserting_before(node):
+            both = graph.create_node("call_function", HipConvBnAct(src.target), (src.args[0],) + tuple(node.args[1:]), {},
+                                     name=src.name + "_bn_act")
+        node.replace_all_uses_with(both)
+        graph.erase_node(node)
+        graph.erase_node(src)
+
+
+def _graph_module(model: nn.Module, graph: torch.fx.Graph, mods, constants: dict, state: BatchesPerForward) -> torch.fx.GraphModule:
+    """Attributes: every submodule the graph calls (the SAME objects: hooks keep firing), what else it reads, the constants."""
+    graph.lint()
+    root = dict(constants)
+    for node in graph.nodes:
+        if node.op == "call_module":
+            root[node.target] = mods[node.target]
+        elif node.op == "get_attr" and node.target not in root:
+            obj = model
+            for part in node.target.split("."):
+                obj = getattr(obj, part)
+            root[node.target] = obj
+    gm = torch.fx.GraphModule(root, graph, class_name=type(model).__name__)
+    gm.train(model.training)
+    gm.batches_per_forward = state      # reset_bn_stats: `gm.batches_per_forward.parts = k` around a k-batch forward
+    # does every normalisation layer with batch statistics go through a per-batch fold?  (only then may batches share a forward)
+    gm.all_batch_statistics_folded = not uses_batch_statistics(gm)
+    return gm
+
+
 def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = False,
                 pool_op: Optional[Callable] = None, conv: Optional[str] = None,
                 inference: bool = False, train_convs: bool = False) -> Optional[torch.fx.GraphModule]:
@@ -462,99 +566,16 @@ def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = Fa
     mods = dict(model.named_modules())
     constants = {}                                    # get_attr targets of the folded scale / shift vectors
     state = BatchesPerForward()                       # train_stats: batches per forwarded tensor, set by the caller
-    folded = 0
-    for node in list(graph.nodes):
-        if node.op != "call_module" or len(node.args) != 1 or node.kwargs:
-            continue
-        bn = mods.get(node.target)
-        per_batch = train_stats and _foldable_train(bn)
-        if not (per_batch or _foldable(bn)):
-            continue
-        tag = node.name
-        if not per_batch:
-            scale, shift = fold_bn(bn)
-            constants["_pleas_scale_%s" % tag] = scale
-            constants["_pleas_shift_%s" % tag] = shift
-
-        chain, res, relu = [node], None, False
-        users = list(node.users)
-        if len(users) == 1 and _is_relu(users[0], mods):
-            chain.append(users[0])
-            relu = True
-        elif len(users) == 1 and _is_add(users[0]) and users[0].args[0] is not users[0].args[1]:
-            add = users[0]
-            add_users = list(add.users)
-            if len(add_users) == 1 and _is_relu(add_users[0], mods):
-                res = add.args[1] if add.args[0] is node else add.args[0]
-                chain += [add, add_users[0]]
-                relu = True
-        window = None
-        if pool_op is not None and relu and res is None and len(chain[-1].users) == 1:
-            pool = next(iter(chain[-1].users))
-            window = _pool_window(pool, mods)
-            if window is not None:
-                chain.append(pool)
-        last = chain[-1]
-        with graph.inserting_before(last):
-            # explicit base names: fx would otherwise derive them from the targets character by character
-            if per_batch:
-                stats = graph.create_node("call_function", _train_fold(bn, tag, state), (node.args[0],), {}, name="bn_stats")
-                s = graph.create_node("call_function", operator.getitem, (stats, 0), {}, name="bn_scale")
-                t = graph.create_node("call_function", operator.getitem, (stats, 1), {}, name="bn_shift")
-            else:
-                s = graph.create_node("get_attr", "_pleas_scale_%s" % tag, (), {}, name="bn_scale")
-                t = graph.create_node("get_attr", "_pleas_shift_%s" % tag, (), {}, name="bn_shift")
-            if window is not None:
-                fused = graph.create_node("call_function", pool_op, (node.args[0], s, t) + window + (relu,), {}, name="bn_act_pool")
-            else:
-                fused = graph.create_node("call_function", op, (node.args[0], s, t, res, relu), {}, name="bn_act")
-        last.replace_all_uses_with(fused)
-        for dead in reversed(chain):
-            graph.erase_node(dead)
-        folded += 1
-    if op is _bn_act and model.training and train_convs:
+    folded = _fold_chains(graph, mods, op, pool_op, train_stats, state, constants)
+    if op is _bn_act and (train_convs or not model.training):
         folded += _own_convs(graph, mods, conv)
-        if train_stats:
+        if model.training and train_stats:
             _conv_stats_pairs(graph, op, pool_op)
-    if op is _bn_act and not model.training:
-        folded += _own_convs(graph, mods, conv)
-        if SOURCE_CONV_BN == "1":
-            # an own convolution consumed by one eval-mode chain only (constants, not per-batch statistics): one launch
-            for node in list(graph.nodes):
-                if not (node.op == "call_function" and node.target is op and isinstance(node.args[0], torch.fx.Node)):
-                    continue
-                src, s = node.args[0], node.args[1]
-                if not (src.op == "call_function" and isinstance(src.target, HipConv) and len(src.users) == 1
-                        and isinstance(s, torch.fx.Node) and s.op == "get_attr"):
-                    continue
-                with graph.inserting_before(node):
-                    both = graph.create_node("call_function", HipConvBnAct(src.target), (src.args[0],) + tuple(node.args[1:]), {},
-                                             name=src.name + "_bn_act")
-                node.replace_all_uses_with(both)
-                graph.erase_node(node)
-                graph.erase_node(src)
-        if inference:
+        if not model.training and SOURCE_CONV_BN == "1":
+            _conv_chain_pairs(graph, op)
+        if not model.training and inference:
             _inference_passes(graph, mods)
-    if folded == 0:
-        return None
-    graph.lint()
-    # the GraphModule's attributes: every submodule the graph calls (the SAME objects, so hooks on them keep firing),
-    # every other attribute it reads, and the folded constants
-    root = dict(constants)
-    for node in graph.nodes:
-        if node.op == "call_module":
-            root[node.target] = mods[node.target]
-        elif node.op == "get_attr" and node.target not in root:
-            obj = model
-            for part in node.target.split("."):
-                obj = getattr(obj, part)
-            root[node.target] = obj
-    gm = torch.fx.GraphModule(root, graph, class_name=type(model).__name__)
-    gm.train(model.training)
-    gm.batches_per_forward = state      # reset_bn_stats: `gm.batches_per_forward.parts = k` around a k-batch forward
-    # does every normalisation layer with batch statistics go through a per-batch fold?  (only then may batches share a forward)
-    gm.all_batch_statistics_folded = not uses_batch_statistics(gm)
-    return gm
+    return _graph_module(model, graph, mods, constants, state) if folded else None
 
 
 def uses_batch_statistics(gm) -> bool:
@@ -562,8 +583,6 @@ def uses_batch_statistics(gm) -> bool:
     InstanceNorm module in train mode (or without running statistics), a functional ``batch_norm`` / ``instance_norm`` with
     ``training`` / ``use_input_stats`` not provably off, or a module outside ``torch.nn`` that has such a submodule?
     Several batches may share a forward only when the answer is no (the fused chains fold train-mode BatchNorm per batch)."""
-    import torch.nn.functional as F
-
     norm = (nn.modules.batchnorm._BatchNorm, nn.modules.instancenorm._InstanceNorm)
     stat = lambda m: isinstance(m, norm) and (m.training or getattr(m, "running_mean", None) is None)
     for n in gm.graph.nodes:

@@ -131,6 +131,30 @@ def test_conv2d_act_splits_a_batch_along_the_sample_axis(ops, mode):
                 assert torch.equal(one, z)
 
 
+def test_conv2d_bn_act_refuses_a_strided_scale_before_any_launch(ops, monkeypatch):
+    """The image operands are checked once for both epilogues: a ``scale`` / ``shift`` that is a strided view (every other element
+    of a longer vector) would be read as if it were dense, so it is refused on the host and the entry point is never reached."""
+    from pleas_merging_amd import _lib
+
+    case = (16, 40, 64, 1, 1, 1, 1, 0, True)      # the smallest of the table
+    assert case in tc.FWD_TABLE and case == min(tc.FWD_TABLE, key=lambda c: c[0] * c[1] * c[2] * c[3] * c[4] * c[5] ** 2)
+    o = _operands(case)
+    N, Cout, Cin, H, W, k, stride, pad, _ = case
+    strided = torch.ones(2 * Cout, device="cuda")[::2]
+    assert strided.numel() == Cout and not strided.is_contiguous()
+
+    def reached(*args):
+        raise AssertionError("the entry point was called")
+
+    for name in ("pleas_conv2d_bn_act_fwd", "pleas_conv2d_act_fwd"):
+        monkeypatch.setattr(_lib.lib(), name, reached, raising=True)
+    for scale, shift in ((strided, o["shift"]), (o["scale"], strided)):
+        with pytest.raises(ops.PleasHipError):
+            ops.conv2d_bn_act(o["x"], o["w"], o["b"], stride, pad, False, scale, shift, None, True)
+        with pytest.raises(ops.PleasHipError):
+            ops.conv2d_act(o["x"], o["w"], o["b"], stride, pad, False, scale, shift, None, True)
+
+
 # ------------------------------------------------------------------------------------------------ 2. pool_gather
 @pytest.mark.parametrize("N", [1, 5])
 @pytest.mark.parametrize("C", [10, 2048])
