@@ -354,6 +354,35 @@ int pleas_linear_fwd(const float* x, const float* w, const float* bias, float* y
 int pleas_column_sum(const float* x, int64_t N, int C, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * uint8 image batches to normalised fp32 NCHW: table lookup, crop and horizontal flip in one pass (csrc/image.hip).
+ *
+ * Replaces: `x.cuda()` of batches that CPU workers have already run through ToTensor / Normalize / RandomCrop /
+ *   RandomHorizontalFlip (pleas/methods/activation_matching.py:121, pleas/methods/pleas_merging.py:266, and the transforms of
+ *   the drivers' datasets): 12 bytes per pixel over PCIe there, 3 here, and no per-image host arithmetic.
+ *   dst[n][c][y][x] = lut[c][ src[n][y0 + y][x0 + xs][c] ],   xs = Wo-1-x when flip[n] != 0, else x;   (y0, x0) = origin[n]
+ * Layout: src uint8, [N][H][W][C] for layout == PLEAS_IMAGE_NHWC, [N][C][H][W] for PLEAS_IMAGE_NCHW, C in 1 .. 4, contiguous,
+ *   any alignment.  dst fp32 [N][C][Ho][Wo] contiguous, 16-byte aligned.  lut DEVICE fp32 [C][256].  origin DEVICE int32 [N][2]
+ *   or NULL = (0, 0).  flip DEVICE uint8 [N] or NULL = none.
+ * Arithmetic: a table lookup and nothing else -- the result has the bits of the table under every compiler flag and is free
+ *   of NaN / inf whenever the table is.  A table built as ((v / 255) - mean[c]) / std[c] in fp32 reproduces ToTensor +
+ *   Normalize bit for bit.
+ * Determinism: no atomics, no floating-point sums; every output element is written once.
+ * Form: the table (at most 4 KB) is copied to LDS once per workgroup.  A row of the output belongs to a team of lanes (the power
+ *   of two at or above Wo / 16) that reads its window byte by byte, the lanes side by side along x, four pixels of loads in
+ *   flight per lane, and writes each plane in 4-byte runs: one path for every C, layout, alignment, crop and flip.  (A second
+ *   path for 16-byte aligned 3-channel rows -- 16-byte loads, de-interleaved in registers, 16-byte stores -- was measured at
+ *   0.97 to 1.01 of the byte path's time and is not kept: profiles/image_batch_fast_vs_byte.json.)
+ * Limits: sizes are `int`, indexing is 64-bit: no 2^30 bound on src or dst.  The origins are NOT checked here: an origin with
+ *   y0 < 0, x0 < 0, y0 > H - Ho or x0 > W - Wo reads outside src; the check is the caller's, on the host, before the upload.
+ * PLEAS_EINVAL, before anything is enqueued: a NULL src, dst or lut with N > 0; C outside 1 .. 4; Ho > H or Wo > W; a
+ *   non-positive H, W, Ho or Wo or a negative N; a dst that is not 16-byte aligned; an unknown layout.  N == 0: PLEAS_OK,
+ *   nothing is enqueued. */
+#define PLEAS_IMAGE_NHWC 0
+#define PLEAS_IMAGE_NCHW 1
+int pleas_image_batch(const uint8_t* src, float* dst, const float* lut, const int32_t* origin, const uint8_t* flip,
+                      int64_t N, int C, int H, int W, int Ho, int Wo, int layout, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * PLeaS layer fitting: fused target/residual/loss pass and grouped weight-gradient launch.
  *
  * Replaces, for merging='perm_gradmask': the output half of get_model_orig_activations

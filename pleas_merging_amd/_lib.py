@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "lib
 EPI_INNER, EPI_NEG_CDIST = 0, 1
 ARITH_FP32, ARITH_SPLIT_BF16, ARITH_SPLIT_BF16_EXACT = 0, 1, 2      # PLEAS_ARITH_*
 LSAP_MAX_N = 4096
+IMAGE_NHWC, IMAGE_NCHW = 0, 1                                       # PLEAS_IMAGE_*
 
 # name -> (restype, argtypes); one row per symbol declared in include/pleas_hip.h
 SIGNATURES = {
@@ -56,6 +57,7 @@ SIGNATURES = {
     "pleas_linear_plan_info": (c_int, [c_int64, c_int, c_int, POINTER(c_int)]),
     "pleas_linear_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "pleas_column_sum": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "pleas_image_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 6 + [c_void_p]),
     "pleas_prof_enable": (None, [c_int]),
     "pleas_prof_select": (None, [ctypes.c_uint]),
     "pleas_prof_reset": (None, []),

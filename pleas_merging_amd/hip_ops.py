@@ -2,7 +2,8 @@
 
 PyTorch is used for device memory and streams only: every function here enqueues a
 hand-written gfx950 kernel on torch's current stream via ctypes.  Inputs must be fp32
-CUDA(=HIP) tensors; anything else raises -- there is no eager/CPU fallback.
+CUDA(=HIP) tensors (``image_batch``: uint8 images); anything else raises -- there is no
+eager/CPU fallback.
 """
 from __future__ import annotations
 
@@ -924,6 +925,95 @@ def column_sum(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     if out.device != x.device or out.numel() != x.shape[1] or not out.is_contiguous():
         raise PleasHipError("column_sum: out must hold %d contiguous floats on x's device" % x.shape[1])
     check(_lib.lib().pleas_column_sum(x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), _stream()), "pleas_column_sum")
+    return out
+
+
+IMAGE_LAYOUTS = {"nhwc": _lib.IMAGE_NHWC, "nchw": _lib.IMAGE_NCHW}
+
+
+def image_table(mean=None, std=None, channels: int = 3) -> torch.Tensor:
+    """The [channels, 256] fp32 table of ``image_batch``, built on the CPU with torch's own fp32 arithmetic:
+    ``table[c][v] = ((v / 255) - mean[c]) / std[c]`` -- ``ToTensor`` then ``Normalize`` as the reference's drivers apply them, so a
+    lookup reproduces their bits by construction.  ``mean=None`` / ``std=None``: that step is left out (both: the plain ``/ 255``
+    of ``ToTensor``).  ``mean`` / ``std``: a number or one per channel.  Move the table to the GPU once (``.to(device)``)."""
+    channels = int(channels)
+    if not 1 <= channels <= 4:
+        raise PleasHipError("image_table: channels must lie in 1 .. 4, got %d" % channels)
+    table = (torch.arange(256, dtype=torch.float32) / 255).repeat(channels, 1)
+    for name, v in (("mean", mean), ("std", std)):
+        if v is None:
+            continue
+        v = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+        if v.numel() not in (1, channels):
+            raise PleasHipError("image_table: %s must hold one value or %d, got %d" % (name, channels, v.numel()))
+        v = v.expand(channels).reshape(channels, 1)
+        table = table.sub(v) if name == "mean" else table.div(v)
+    return table.contiguous()
+
+
+def image_batch(src_u8: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None, origin=None, flip=None,
+                size: Optional[Tuple[int, int]] = None, layout: str = "nhwc") -> torch.Tensor:
+    """uint8 images on the GPU to normalised fp32 [N, C, Ho, Wo] in one pass (``pleas_image_batch``):
+    ``out[n, c, y, x] = table[c, src[n, y0 + y, x0 + xs, c]]`` with ``xs = Wo - 1 - x`` for a flipped sample, else ``x``.
+
+    ``src_u8``: contiguous uint8 on the GPU, [N, H, W, C] (``layout="nhwc"``) or [N, C, H, W] (``"nchw"``), C in 1 .. 4, any
+    alignment.  ``table``: ``image_table(...)`` on the same device.  ``size=(Ho, Wo)``: the window (default: the whole image).
+    ``origin``: HOST integers [N, 2], ``(y0, x0)`` per sample (default ``(0, 0)``), checked HERE against ``[0, H - Ho]`` x
+    ``[0, W - Wo]`` and then uploaded -- the kernel does not look again.  ``flip``: HOST flags [N].  ``out``: a contiguous fp32
+    [N, C, Ho, Wo] tensor on the device, 16-byte aligned (allocated when not given)."""
+    if not torch.is_tensor(src_u8) or src_u8.dtype != torch.uint8:
+        raise PleasHipError("image_batch: src must be a uint8 tensor (got %s)" % getattr(src_u8, "dtype", type(src_u8)))
+    if layout not in IMAGE_LAYOUTS:
+        raise PleasHipError("image_batch: layout must be one of %r, got %r" % (tuple(IMAGE_LAYOUTS), layout))
+    if src_u8.dim() != 4 or not src_u8.is_contiguous():
+        raise PleasHipError("image_batch: src must be a contiguous 4-d tensor, got shape %s" % (tuple(src_u8.shape),))
+    N, (H, W, C) = src_u8.shape[0], (src_u8.shape[1:] if layout == "nhwc" else (src_u8.shape[2], src_u8.shape[3], src_u8.shape[1]))
+    if not 1 <= C <= 4:
+        raise PleasHipError("image_batch: %d channels (layout %r); the kernel takes 1 .. 4" % (C, layout))
+    if H < 1 or W < 1 or H >= 1 << 31 or W >= 1 << 31:
+        raise PleasHipError("image_batch: empty or oversized images, shape %s" % (tuple(src_u8.shape),))
+    Ho, Wo = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if not (1 <= Ho <= H and 1 <= Wo <= W):
+        raise PleasHipError("image_batch: the window %s must be positive and fit inside the %d x %d image" % ((Ho, Wo), H, W))
+    if origin is not None:
+        if torch.is_tensor(origin) and origin.is_cuda:
+            raise PleasHipError("image_batch: origins are checked on the host: pass a CPU tensor or a sequence")
+        origin = torch.as_tensor(origin)
+        if origin.dtype.is_floating_point or origin.dtype == torch.bool or tuple(origin.shape) != (N, 2):
+            raise PleasHipError("image_batch: origin must hold integers of shape (%d, 2), got %s %s" % (N, origin.dtype, tuple(origin.shape)))
+        origin = origin.to(torch.int64)
+        if N and (int(origin.min()) < 0 or int(origin[:, 0].max()) > H - Ho or int(origin[:, 1].max()) > W - Wo):
+            raise PleasHipError("image_batch: origin outside [0, %d] x [0, %d] (image %d x %d, window %d x %d)"
+                                % (H - Ho, W - Wo, H, W, Ho, Wo))
+    if flip is not None:
+        if torch.is_tensor(flip) and flip.is_cuda:
+            raise PleasHipError("image_batch: flip flags are host values: pass a CPU tensor or a sequence")
+        flip = torch.as_tensor(flip)
+        if tuple(flip.shape) != (N,):
+            raise PleasHipError("image_batch: flip must hold %d flags, got shape %s" % (N, tuple(flip.shape)))
+        flip = flip.ne(0).to(torch.uint8)
+    if out is not None and (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, C, Ho, Wo) or not out.is_contiguous()
+                            or out.data_ptr() % 16):
+        raise PleasHipError("image_batch: out must be a contiguous, 16-byte aligned fp32 tensor of shape %s on the GPU"
+                            % ((N, C, Ho, Wo),))
+    if not src_u8.is_cuda:
+        raise PleasHipError("HIP path needs tensors on the GPU (got device %s); no CPU fallback" % src_u8.device)
+    _need_gpu(table)
+    if table.device != src_u8.device or tuple(table.shape) != (C, 256) or not table.is_contiguous():
+        raise PleasHipError("image_batch: table must be a contiguous fp32 [%d, 256] tensor on src's device" % C)
+    if out is None:
+        out = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=src_u8.device)
+    elif out.device != src_u8.device:
+        raise PleasHipError("image_batch: out must be on src's device")
+    if N == 0:
+        return out
+    dev = src_u8.device
+    origin_d = origin.to(torch.int32).contiguous().to(dev) if origin is not None else None
+    flip_d = flip.contiguous().to(dev) if flip is not None else None
+    check(_lib.lib().pleas_image_batch(src_u8.data_ptr(), out.data_ptr(), table.data_ptr(),
+                                       origin_d.data_ptr() if origin_d is not None else None,
+                                       flip_d.data_ptr() if flip_d is not None else None, N, C, H, W, Ho, Wo,
+                                       IMAGE_LAYOUTS[layout], _stream()), "pleas_image_batch")
     return out
 
 
