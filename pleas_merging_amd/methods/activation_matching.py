@@ -16,8 +16,6 @@ the reference's plug points (generic path).
 """
 from __future__ import annotations
 
-import os
-
 from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
 import torch
@@ -28,6 +26,7 @@ from ..core.solvers import hip_solve_lsa, hip_solve_minimax_assignment
 from ..core.utils import Axis, Permutation, PermutationSpec
 from .. import hip_ops
 from ..hip_ops import cross_features_cdist, cross_features_inner_product  # noqa: F401  (public plug-ins)
+from .data_parallel import _collectives_on, _dist_info, _force_collectives, allreduce_sum_  # noqa: F401  (their home; imported from here too)
 
 _FUSED_EPILOGUE = {}  # callable -> epilogue id, filled below
 
@@ -405,32 +404,6 @@ def build_fused_module(spec: PermutationSpec, model1: nn.Module, model2: nn.Modu
 
 
 # ------------------------------------------------------------------------------------------ cost accumulation
-def _dist_info():
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        return dist.get_rank(), dist.get_world_size()
-    # PLEAS_EMULATE_WORLD=N (profiling aid, bench.py --emulate-world): this process does rank 0's share of an N-rank job
-    # with the collectives skipped -- the per-rank critical path of a multi-GPU run, timed on one GPU.  The RESULTS of such
-    # a run are partial sums and must not be used.
-    emulated = int(os.environ.get("PLEAS_EMULATE_WORLD", "0") or 0)
-    return (0, emulated) if emulated > 1 else (0, 1)
-
-
-def _collectives_on() -> bool:
-    import torch.distributed as dist
-
-    return dist.is_available() and dist.is_initialized()
-
-
-def _force_collectives() -> bool:
-    """PLEAS_FORCE_COLLECTIVES=1 with ``torch.distributed`` initialised: the path's exchange steps are issued even when
-    the group has ONE rank (where a sum over ranks is the identity), so that the very calls an N-rank job makes --
-    ``all_reduce`` of the cost arena and of the gradient arena, ``reduce_scatter_tensor`` / ``all_gather_into_tensor``
-    under ``shard_optimizer`` -- go through RCCL on a one-GPU box and can be timed there."""
-    return os.environ.get("PLEAS_FORCE_COLLECTIVES", "0") not in ("", "0") and _collectives_on()
-
-
 def _unfolded_batch_statistics(gm: nn.Module) -> bool:
     """Does the twin graph still CALL something that uses batch statistics?  The fused chains fold a train-mode BatchNorm2d
     per batch (``pleas_bn_train_fold_batches``: exact on a concatenated forward); a module -- or a functional
@@ -452,16 +425,6 @@ def shard_batches(dataloader, num_batches: int, rank: int, world: int):
     for b, (batch, _) in enumerate(zip(dataloader, range(num_batches))):
         if b % world == rank:
             yield batch
-
-
-def allreduce_sum_(flat: torch.Tensor, world: int) -> torch.Tensor:
-    """The one exchange step of the matching path: sum the flat cost arena over ranks
-    (RCCL over xGMI under the ``nccl`` backend; gloo in the CPU tests)."""
-    if (world > 1 and _collectives_on()) or _force_collectives():
-        import torch.distributed as dist
-
-        dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-    return flat
 
 
 def compute_matching_costs(spec: PermutationSpec, gm_cross: nn.Module, dataloader, num_batches: int,

@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from ..core.utils import Axis, Permutation, PermutationSpec
+from .data_parallel import _dist_info
 
 
 BN_RESET_BACKBONES = ("modules", "hip")
@@ -67,8 +68,6 @@ def reset_bn_stats(model: nn.Module, dataloader: Iterable, num_batches: int = 10
     a flat buffer per statistic gives every rank the sequential result (``momentum=None``, the cumulative average: the
     plain mean of the batches' statistics).
     """
-    from .activation_matching import _dist_info
-
     if backbone not in BN_RESET_BACKBONES:
         raise ValueError("reset_bn_stats: backbone must be one of %r, got %r" % (BN_RESET_BACKBONES, backbone))
     if device is None:

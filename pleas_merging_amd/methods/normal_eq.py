@@ -18,17 +18,21 @@ non-positive pivot is redone in fp64 on the vendor solver and counted in ``info[
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List
 
 import torch
+import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
-from .pleas_merging import PleasFitter, _LayerPlan, dp_sum_
+from .data_parallel import _dist_info, dp_sum_
+from .pleas_merging import PleasFitter, _LayerFitter, _LayerPlan  # noqa: F401  (PleasFitter: importable from here as before)
 
 
-class NormalEqFitter(PleasFitter):
-    """Accumulates A and B^T for every merged layer; ``solve`` writes the closed-form weights."""
+class NormalEqFitter(_LayerFitter):
+    """Accumulates A and B^T for every merged layer; ``solve`` writes the closed-form weights.  Takes ``PleasFitter``'s
+    arguments and allocates none of Adam's state (gradient arenas, moments, schedule, losses, replay record)."""
 
     def __init__(self, *args, ridge: float = 1e-6, shard_solve: bool = True, **kwargs):
         super().__init__(*args, **kwargs)
@@ -41,40 +45,29 @@ class NormalEqFitter(PleasFitter):
         # repeated on every one (0.2 s of an 8-rank job's 1.6 s)
         self.shard_solve = bool(shard_solve)
         dev = self.device
-        self.K: List[int] = []
-        for plan in self.plans:
-            w = plan.w_shape
-            self.K.append(int(w[1] * (w[2] * w[3] if len(w) == 4 else 1)))
+        self.K: List[int] = [int(math.prod(plan.w_shape[1:])) for plan in self.plans]
+        cout = [plan.w_shape[0] for plan in self.plans]
         self.A_flat = torch.zeros(sum(k * k for k in self.K), dtype=torch.float32, device=dev)
-        self.B_flat = torch.zeros(sum(k * p.w_shape[0] for k, p in zip(self.K, self.plans)), dtype=torch.float32, device=dev)
-        self.A: List[torch.Tensor] = []
-        self.Bt: List[torch.Tensor] = []   # [Cout][K] with kernel-position-major columns
-        oa = ob = 0
-        for k, plan in zip(self.K, self.plans):
-            self.A.append(self.A_flat[oa:oa + k * k].view(k, k))
-            oa += k * k
-            co = plan.w_shape[0]
-            self.Bt.append(self.B_flat[ob:ob + co * k].view(co, k))
-            ob += co * k
+        self.B_flat = torch.zeros(sum(k * co for k, co in zip(self.K, cout)), dtype=torch.float32, device=dev)
+        # per layer, views of the two arenas: A [K][K]; B^T [Cout][K] with kernel-position-major columns
+        self.A: List[torch.Tensor] = [a.view(k, k) for a, k in zip(self.A_flat.split([k * k for k in self.K]), self.K)]
+        self.Bt: List[torch.Tensor] = [b.view(co, k) for b, k, co in
+                                       zip(self.B_flat.split([k * co for k, co in zip(self.K, cout)]), self.K, cout)]
         # bias columns (Linear layers): column sums of U, of op, and the row count
         self.bias_stats: Dict[int, List[torch.Tensor]] = {
             i: [torch.zeros(self.K[i], device=dev), torch.zeros(p.w_shape[0], device=dev), torch.zeros(1, device=dev)]
             for i, p in enumerate(self.plans) if p.b is not None}
         self.neq = self.ops.NormalEqBatch(dev)
-        self.batches_seen = 0
-        self._slice_batch = False   # data parallel here = whole batches per rank (train_normal_eq), never sample slices
+        self.sources._slice_batch = False   # data parallel here = whole batches per rank (train_normal_eq), never sample slices
 
     def _hip_geometry_ok(self, plan: _LayerPlan, ip: torch.Tensor) -> bool:
-        mod = plan.mod
-        if not plan.is_conv:
-            return ip.dim() == 2
-        return (mod.groups == 1 and mod.dilation == (1, 1) and mod.stride[0] == mod.stride[1]
-                and mod.padding[0] == mod.padding[1] and ip.shape[1] >= 16)
+        return ip.shape[1] >= 16 if plan.is_conv else ip.dim() == 2       # (any other Conv2d geometry was refused in __init__)
 
     def _step(self, x: torch.Tensor, next_x=None) -> None:
-        """Accumulate one batch (no parameter update); driven by :meth:`PleasFitter.step`."""
+        """Accumulate one batch (no parameter update); driven by :meth:`_LayerFitter.step`."""
         ops = self.ops
         self._begin_update(x, next_x)
+        (in1, in2), (out1, out2) = self.gen.taps.inputs, self.gen.taps.outputs
         KP = ops.WgradBatch.ACCUMULATE | ops.WgradBatch.KPOS_MAJOR
         # The stacked objectives (reg_mean / perm_separatels / perm_mixedls, reference :125-145) put TWO half-batches under
         # the same weights: A and B are the sums over both.  Each half is its own round of grouped launches (two entries of
@@ -82,24 +75,20 @@ class NormalEqFitter(PleasFitter):
         for h in range(len(self.plans[0].halves) if self.plans else 0):
             for idx, plan in enumerate(self.plans):
                 name = plan.name
-                if name not in self.t1_in or name not in self.t2_in:
+                if name not in in1 or name not in in2:
                     if h == 0:
                         print("Key error on %s" % name)
                     continue
                 mod = plan.mod
                 in_maps, out_maps = plan.halves[h]
-                grouped = self._hip_geometry_ok(plan, self.t1_in[name]) and plan.b is None
+                grouped = self._hip_geometry_ok(plan, in1[name]) and plan.b is None
                 merge = self.merge.add if grouped else ops.merge_blocks     # grouped: filled by merge.flush() below
-                ip = merge(self.t1_in[name], self.t2_in[name], 1, *in_maps)
-                op = merge(self.t1_out[name], self.t2_out[name], 1, *out_maps)
+                ip = merge(in1[name], in2[name], 1, *in_maps)
+                op = merge(out1[name], out2[name], 1, *out_maps)
                 if self._hip_geometry_ok(plan, ip):
-                    if plan.is_conv:
-                        geo = (tuple(mod.kernel_size), mod.stride[0], mod.padding[0])
-                        self.neq.add(ip, self.A[idx], *geo)
-                        self.wgrad.add(op, ip, self.Bt[idx], *geo, flags=KP)
-                    else:
-                        self.neq.add(ip, self.A[idx])
-                        self.wgrad.add(op, ip, self.Bt[idx], flags=KP)
+                    geo = (tuple(mod.kernel_size), mod.stride[0], mod.padding[0]) if plan.is_conv else ()
+                    self.neq.add(ip, self.A[idx], *geo)
+                    self.wgrad.add(op, ip, self.Bt[idx], *geo, flags=KP)
                 else:  # stem (3 input channels) / exotic geometry: tiny K, vendor GEMM on an explicit im2col
                     U = F.unfold(ip, mod.kernel_size, mod.dilation, mod.padding, mod.stride)      # B, (ci,kh,kw), L
                     cin, r = ip.shape[1], mod.kernel_size[0] * mod.kernel_size[1]
@@ -130,7 +119,6 @@ class NormalEqFitter(PleasFitter):
             self.merge.flush()
             self.neq.flush()
             self.wgrad.flush()
-        self.batches_seen += 1
         self._end_update()
 
     @torch.no_grad()
@@ -146,15 +134,12 @@ class NormalEqFitter(PleasFitter):
         # own and takes the others' (the layers' image sizes; the batch size plays no part)
         mine = self.neq.seen()
         geos = {i: mine[A.data_ptr()][1] for i, A in enumerate(self.A) if A.data_ptr() in mine}
-        if self.world > 1:
-            import torch.distributed as dist
-
-            if dist.is_initialized():
-                every = [None] * dist.get_world_size()
-                dist.all_gather_object(every, geos)
-                for other in every:
-                    for i, g in other.items():
-                        geos.setdefault(i, g)
+        if self.world > 1 and dist.is_initialized():
+            every = [None] * dist.get_world_size()
+            dist.all_gather_object(every, geos)
+            for other in every:
+                for i, g in other.items():
+                    geos.setdefault(i, g)
         self.neq.finalize([(self.A[i], g) for i, g in sorted(geos.items())])
         info: Dict[str, float] = {}
         jobs, finals = [], []   # (W, rows, free, A_FF, rhs, A_FF backup) per solve; (plan, W, layout) per layer
@@ -164,22 +149,17 @@ class NormalEqFitter(PleasFitter):
                 info[plan.name] = float(self.K[idx])
                 continue
             K, co = self.K[idx], plan.w_shape[0]
-            A = self.A[idx]
-            A = torch.tril(A) + torch.tril(A, -1).t()          # kernels fill the lower triangle only
+            A = torch.tril(self.A[idx]) + torch.tril(self.A[idx], -1).t()          # kernels fill the lower triangle only
             Bt = self.Bt[idx]
-            if plan.kpos:                                      # the arena already holds [Cout][KH][KW][Cin]
-                to_kpos = lambda t, co=co, K=K: t.reshape(co, K)
-                from_kpos = lambda t, shp=tuple(plan.w.shape): t.reshape(shp)
-            elif len(plan.w_shape) == 4:
+            if len(plan.w_shape) == 4 and not plan.kpos:
                 cin, r = plan.w_shape[1], plan.w_shape[2] * plan.w_shape[3]
                 to_kpos = lambda t, co=co, cin=cin, r=r, K=K: t.reshape(co, cin, r).permute(0, 2, 1).reshape(co, K)
                 from_kpos = lambda t, co=co, cin=cin, r=r, shp=plan.w_shape: \
                     t.reshape(co, r, cin).permute(0, 2, 1).reshape(shp)
-            else:
+            else:                                              # Linear, or the arena already holds [Cout][KH][KW][Cin]
                 to_kpos = lambda t, co=co, K=K: t.reshape(co, K)
-                from_kpos = lambda t, shp=plan.w_shape: t.reshape(shp)
-            n_w = plan.w.numel()
-            mask = to_kpos(self.mask[plan.off_w:plan.off_w + n_w])
+                from_kpos = lambda t, shp=tuple(plan.w.shape): t.reshape(shp)
+            mask = to_kpos(self.mask[plan.off_w:plan.off_w + plan.w.numel()])
             w0 = to_kpos(plan.w)
             if plan.b is not None:                             # augmented system for the bias column
                 su, sy, m = self.bias_stats[idx]
@@ -228,8 +208,6 @@ def exchange_solved_(arena: torch.Tensor, layer_views: List[List[torch.Tensor]],
     """After a layer-sharded solve: every layer's parameters (views of ``arena``) were written by exactly one rank.  The
     others' layers are zeroed here and the arena is summed ONCE over the ranks -- x + 0 is exact, so every rank ends with
     the owner's bits.  Without peers (PLEAS_EMULATE_WORLD: a projection, not a result) nothing is zeroed."""
-    import torch.distributed as dist
-
     if world <= 1 or not dist.is_initialized():
         return
     for views, r in zip(layer_views, owner):
@@ -288,8 +266,6 @@ def train_normal_eq(dataloader, model1, model2, model3, spec, perm, costs, budge
                     num_classes, model_type, verbose, ridge: float = 1e-6, merging: str = "perm_gradmask"):
     """Same data consumption as the Adam loop (``MAX_STEPS + 1`` batches of one pass, reference :368-373);
     with ``torch.distributed`` initialised, rank r accumulates batches ``b % world == r``."""
-    from .activation_matching import _dist_info
-
     fit = NormalEqFitter(model1, model2, model3, spec, perm, costs, budget_ratios, MAX_STEPS, 5e-4, separate_classifier,
                          num_classes, model_type, merging=merging, ridge=ridge)
     fit.rank, fit.world = _dist_info()

@@ -25,10 +25,18 @@ MI355X design of one Adam step (13 ms for a ResNet-101 pair at batch 16)
   * all parameters, gradients, masks and Adam moments live in flat fp32 arenas (k x k weights kernel-position-major),
     so the masked Adam update of the whole model is ONE ``pleas_masked_adam`` launch and the data-parallel gradient
     exchange is one all-reduce.
+
+Who owns what
+  * ``frozen_sources.py``: the two source models, their taps and side streams, the queue of ``Generation``s (batch +
+    ``SourceTaps``) whose forwards are in flight; ``data_parallel.py``: rank / world and every collective;
+  * ``_LayerFitter``: what both solvers need -- the sources, the parameter arena ``p`` with its ``mask``, the ``plans``, the
+    ``merge`` / ``wgrad`` batches, the update stream, the loop (``steps`` / ``step``), the generation being read (``gen``);
+  * ``PleasFitter``: what Adam adds -- gradient arenas and per-plan gradient views, moments, schedule, losses, the
+    grouped forward, and the ``_UpdateRecord`` a later update of the same shape replays (``_replay``);
+  * ``NormalEqFitter`` (``normal_eq.py``): the ``A`` / ``B`` arenas and the solve, none of Adam's state.
 """
 from __future__ import annotations
 
-import collections
 import contextlib
 import math
 from typing import Dict, List, Optional, Tuple
@@ -37,7 +45,11 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import hip_ops
 from ..core.utils import Axis, get_attr
+from .data_parallel import _SPIN, _emulated_collective, _force_collectives, dp_all_gather_, dp_reduce_scatter_, dp_slice, dp_sum_  # noqa: F401
+from .frozen_sources import (ActivationTap, FrozenSources, Generation, SourceTaps, TapDict, _TapView,  # noqa: F401
+                             prepare_sources, tap_pointers)
 from .partial_matching import block_maps, get_blocks, spread_blocks
 
 
@@ -78,113 +90,6 @@ def _square_conv(mod: nn.Conv2d) -> bool:
             and mod.padding[0] == mod.padding[1] and mod.kernel_size[0] == mod.kernel_size[1])
 
 
-def prepare_sources(model1: nn.Module, model2: nn.Module):
-    """The two frozen sources as the fitter runs them (eval mode, BatchNorm / add / ReLU chains folded into one HIP pass
-    each; a model that cannot be rewritten is returned as it is).  Needs neither the permutation nor the merged model,
-    so it can be built early and handed to ``PleasFitter(fused_sources=...)``."""
-    from .source_forward import fuse_bn_act
-
-    model1.eval()
-    model2.eval()
-    return fuse_bn_act(model1) or model1, fuse_bn_act(model2) or model2
-
-
-class TapDict(dict):
-    """name -> tensor of one forward.  ``packs`` caches, per list of names, the device addresses and per-sample strides of
-    those tensors (``tap_pointers``)."""
-
-    __slots__ = ("packs",)
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.packs = {}
-
-
-class _TapView:
-    """The taps of ONE update inside a grouped source forward: samples ``lo:hi`` of every tensor of ``base``, sliced on
-    access (an update touches ~420 of them; slicing all of them ahead of time was 0.6 ms of host time per update)."""
-
-    __slots__ = ("base", "lo", "hi")
-
-    def __init__(self, base: TapDict, lo: int, hi: int):
-        self.base, self.lo, self.hi = base, lo, hi
-
-    def __getitem__(self, name):
-        return self.base[name][self.lo:self.hi]
-
-    def __contains__(self, name):
-        return name in self.base
-
-    def __len__(self):
-        return len(self.base)
-
-    def keys(self):
-        return self.base.keys()
-
-    def items(self):
-        return ((k, v[self.lo:self.hi]) for k, v in self.base.items())
-
-
-def tap_pointers(taps, names: tuple):
-    """Device addresses (numpy uint64) of ``taps[name]`` for ``name`` in ``names`` -- of the update's first sample when
-    ``taps`` is a view into a grouped forward.  The per-forward part is computed once per (forward, names)."""
-    import numpy as np
-
-    base, lo = (taps.base, taps.lo) if isinstance(taps, _TapView) else (taps, 0)
-    packs = getattr(base, "packs", None)
-    hit = packs.get(id(names)) if packs is not None else None
-    if hit is None or hit[0] is not names:
-        ts = [base[k] for k in names]
-        if not all(t.is_contiguous() and t.dtype == torch.float32 for t in ts):
-            return None
-        hit = (names, np.array([t.data_ptr() for t in ts], dtype=np.uint64),
-               np.array([t.stride(0) * 4 if t.dim() > 0 else 0 for t in ts], dtype=np.uint64))
-        if packs is not None:
-            packs[id(names)] = hit
-    return hit[1] + np.uint64(lo) * hit[2] if lo else hit[1]
-
-
-class ActivationTap:
-    """Forward hooks on every Conv2d / Linear / LayerNorm of a model that keep the module's
-    input and output of the latest forward (reference keeps inputs only, :197-231)."""
-
-    KINDS = (nn.Conv2d, nn.Linear, nn.LayerNorm)
-
-    def __init__(self, model: nn.Module):
-        self.inputs: Dict[str, torch.Tensor] = TapDict()
-        self.outputs: Dict[str, torch.Tensor] = TapDict()
-        self.handles = []
-        for name, mod in model.named_modules():
-            if isinstance(mod, self.KINDS):
-                self.handles.append(mod.register_forward_hook(self._hook(name)))
-
-    def _hook(self, name):
-        def hook(module, inp, out):
-            if isinstance(inp, tuple):
-                assert len(inp) == 1
-                inp = inp[0]
-            self.inputs[name] = inp
-            self.outputs[name] = out
-
-        return hook
-
-    def clear(self):
-        self.inputs.clear()
-        self.outputs.clear()
-
-    def take(self):
-        """Hand over the tensors of the latest forward and start a new generation (the hooks look the dicts up on
-        every call, so the next forward fills the fresh ones)."""
-        got = (self.inputs, self.outputs)
-        self.inputs, self.outputs = TapDict(), TapDict()
-        return got
-
-    def remove(self):
-        for h in self.handles:
-            h.remove()
-        self.handles = []
-
-
 def cosine_lrs(base_lr: float, t_max: int, n: int) -> List[float]:
     """Learning rate used by update 0..n-1 under ``CosineAnnealingLR(T_max=t_max)`` stepped once
     per update, evaluated with torch's recursive form so the doubles match the reference
@@ -202,8 +107,7 @@ def cosine_lrs(base_lr: float, t_max: int, n: int) -> List[float]:
 
 # ------------------------------------------------------------------------------------------ per-layer plan
 class _LayerPlan:
-    __slots__ = ("name", "mod", "is_conv", "w", "b", "gw", "gb", "gw2", "gb2", "in_maps", "out_maps", "halves", "w_shape",
-                 "off_w", "kpos", "vendor")
+    __slots__ = ("name", "mod", "is_conv", "w", "b", "gw", "gb", "gw2", "gb2", "halves", "w_shape", "off_w", "kpos")
 
 
 def _identity_block(n: int):
@@ -267,255 +171,18 @@ def half_maps(mode: str, bi, bo, cin: int, cout_src: int, device):
     return [(side(bi, h, mixed), side(bo, h, False)) for h in (0, 1)]
 
 
-def dp_slice(x: torch.Tensor, rank: int, world: int) -> torch.Tensor:
-    """Rank's share of one batch under data-parallel PLeaS: contiguous, equal sample chunks."""
-    if world == 1:
-        return x
-    if x.shape[0] % world:
-        raise RuntimeError("batch of %d samples does not split over %d ranks" % (x.shape[0], world))
-    return x.chunk(world)[rank]
+_pad4 = lambda n: (n + 3) // 4 * 4   # every tensor starts 16-byte aligned inside the arenas (vector loads)
 
 
-def dp_sum_(flat: torch.Tensor, world: int, share: float = 1.0) -> torch.Tensor:
-    """Sum of the flat gradient arena over ranks (ONE collective per update).  Each rank scales its
-    residual by 2 / (local numel * world), so the sum IS the gradient of the full-batch mean."""
-    from .activation_matching import _force_collectives
-
-    if world > 1 or _force_collectives():
-        import torch.distributed as dist
-
-        if dist.is_initialized():
-            dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-        else:                           # PLEAS_EMULATE_WORLD (activation_matching._dist_info): no peers
-            _emulated_collective(flat, share)
-    return flat
-
-
-def dp_reduce_scatter_(flat: torch.Tensor, mine: torch.Tensor, rank: int, world: int) -> torch.Tensor:
-    """Sum of ``flat`` over ranks, of which this rank needs only its ``rank``-th 1/world slice: ONE reduce-scatter into
-    ``mine`` (RCCL); backends without it (gloo, the single-GPU rehearsals) all-reduce and take the slice."""
-    import torch.distributed as dist
-
-    n = flat.numel() // world
-    if not dist.is_initialized():              # PLEAS_EMULATE_WORLD: no peers
-        return flat[rank * n:(rank + 1) * n]
-    if dist.get_backend() == "nccl":
-        dist.reduce_scatter_tensor(mine, flat, op=dist.ReduceOp.SUM)
-        return mine
-    dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-    return flat[rank * n:(rank + 1) * n]
-
-
-def dp_all_gather_(flat: torch.Tensor, rank: int, world: int) -> None:
-    """Every rank's updated 1/world slice of ``flat`` to all ranks, in place (ONE all-gather)."""
-    import torch.distributed as dist
-
-    if not dist.is_initialized():
-        return
-    n = flat.numel() // world
-    mine = flat[rank * n:(rank + 1) * n].clone()       # the collective must not read from its own output
-    if dist.get_backend() == "nccl":
-        dist.all_gather_into_tensor(flat, mine)
-    else:
-        dist.all_gather(list(flat.chunk(world)), mine)
-
-
-_SPIN = {}
-
-
-def _emulated_collective(flat: torch.Tensor, share: float = 1.0) -> None:
-    """Profiling aid: with PLEAS_EMULATE_ALLREDUCE_US=T the stream is held for ``share`` * T microseconds where the
-    all-reduce would run (a spin kernel on one CU; T = the whole gradient arena), so that what overlaps a collective
-    can be studied on one GPU."""
-    import os
-
-    us = float(os.environ.get("PLEAS_EMULATE_ALLREDUCE_US", "0") or 0) * share
-    if us <= 0 or not flat.is_cuda:
-        return
-    if "per_us" not in _SPIN:           # calibrate the spin kernel's cycle unit once
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(1000)
-        a.record()
-        torch.cuda._sleep(2_000_000)
-        b.record()
-        b.synchronize()
-        _SPIN["per_us"] = 2_000_000 / (a.elapsed_time(b) * 1e3)
-    torch.cuda._sleep(int(us * _SPIN["per_us"]))
-
-
-class FrozenSources:
-    """The two frozen source models as the PLeaS loop runs them: eval mode, BatchNorm / add / ReLU chains folded into one
-    HIP pass each (``source_forward.py``), taps on every Conv2d / Linear, each model on its own side stream.  A forward
-    produces a GENERATION ``(device batch, taps of model1, taps of model2, events)``; ``queue`` holds the generations whose
-    forwards are enqueued, in update order, as ``(batch as passed,) + generation``.
-
-    Nothing here depends on the permutation or on the merged model, so the object can be built -- and the first forwards
-    enqueued (``prefetch``) -- while the LAP kernel is still running; ``PleasFitter(sources=...)`` then takes it over."""
-
-    def __init__(self, model1: nn.Module, model2: nn.Module, data_parallel: bool = False, fuse: bool = True,
-                 overlap: bool = True, fused=None):
-        from .. import hip_ops
-        from .activation_matching import _dist_info
-
-        self.ops = hip_ops
-        self.rank, self.world = _dist_info() if data_parallel else (0, 1)
-        self.device = next(iter(model1.parameters())).device
-        if self.device.type != "cuda":
-            raise hip_ops.PleasHipError("pleas_merging.train: source models must be on the GPU (got %s)" % self.device)
-        self.tap1, self.tap2 = ActivationTap(model1), ActivationTap(model2)
-        model1.eval()
-        model2.eval()
-        # the hooked Conv2d / Linear modules are shared with the rewritten graphs, so the taps see the same tensors
-        self.src1, self.src2 = model1, model2
-        if fused is not None:               # built ahead of time (prepare_sources)
-            self.src1, self.src2 = fused
-        elif fuse:
-            self.src1, self.src2 = prepare_sources(model1, model2)
-        # The two source forwards are independent chains of small kernels (one conv of a batch-16 ResNet fills a
-        # fraction of 256 CUs).  Each source gets its own stream: their chains then also run NEXT TO the big grouped
-        # kernels of an update when they are enqueued ahead of it.  Equal priorities: favouring either side was slower
-        # (chain first 8.7 s, update first 11.5 s).
-        self._side_streams = (hip_ops.role_stream(self.device, "model1"),
-                              hip_ops.role_stream(self.device, "model2")) if overlap else None
-        self._src_events = None
-        self._slice_batch = True   # data parallel: every update splits its batch's samples over the ranks
-        self.queue: collections.deque = collections.deque()
-        self._staged: dict = {}    # id(pinned host batch) -> (batch, device copy, event): copies started ahead of their forward
-
-    def stage(self, batches) -> None:
-        """Start the host -> device copies of PINNED host batches now (copy stream); the forward that takes a batch later
-        only waits for its event.  ``steps`` stages the group AFTER the one it launches: enqueued together with a group's
-        forwards, a copy would sit behind that group's kernels in a shared hardware queue and surface when it is needed."""
-        for b in batches:
-            if torch.is_tensor(b) and not b.is_cuda and b.is_pinned() and id(b) not in self._staged:
-                self._staged[id(b)] = (b,) + self.ops.h2d_start(b, self.device)
-
-    def _to_device(self, b: torch.Tensor) -> torch.Tensor:
-        hit = self._staged.pop(id(b), None) if torch.is_tensor(b) else None
-        if hit is not None and hit[0] is b:
-            return self.ops.h2d_finish(hit[1], hit[2], self.device)
-        return self.ops.to_device_async(b, self.device)
-
-    def launch(self, x: torch.Tensor, parts: int = 1, after_current: bool = True):
-        """Enqueue both source forwards for ``x``; returns the generation (device batch, taps, events) the update will
-        consume.  ``parts`` > 1: ``x`` is that many batches back to back, each of which is sample-sliced on its own."""
-        x = self._to_device(x)
-        if self._slice_batch:
-            if parts > 1 and self.world > 1:
-                h = x.shape[0] // parts
-                x = torch.cat([dp_slice(x[i * h:(i + 1) * h], self.rank, self.world) for i in range(parts)], 0)
-            else:
-                x = dp_slice(x, self.rank, self.world)
-        self.run_eager(x, after_current)
-        events = self._src_events
-        self._src_events = None
-        return (x, self.tap1.take(), self.tap2.take(), events)
-
-    @torch.no_grad()
-    def launch_group(self, run: List[torch.Tensor], after_current: bool = True) -> None:
-        """One source forward for several batches; their generations (views of its taps) join the queue."""
-        first = self._side_streams[0] if (self._side_streams is not None and not after_current) else None
-        with (torch.cuda.stream(first) if first is not None else contextlib.nullcontext()):
-            # pinned host batches travel on a copy stream while the previous group's updates run (hip_ops.to_device_async)
-            both = torch.cat([self._to_device(b) for b in run], 0)
-            xdev, (in1, out1), (in2, out2), events = self.launch(both, parts=len(run), after_current=after_current)
-        n = xdev.shape[0] // len(run)
-        for i, b in enumerate(run):
-            lo, hi = i * n, (i + 1) * n
-            self.queue.append((b, xdev, (_TapView(in1, lo, hi), _TapView(out1, lo, hi)),
-                               (_TapView(in2, lo, hi), _TapView(out2, lo, hi)), events))
-
-    @torch.no_grad()
-    def prefetch(self, batches, group: Optional[int] = None, max_groups: int = 1, memory_fraction: float = 0.5) -> int:
-        """Enqueue the source forwards of the first batches NOW, on the side streams only -- not ordered after the work
-        already queued on the current stream, which is the point: called from ``activation_matching(while_solving=...)``
-        they run beside the LAP kernel (one workgroup per problem, 71 of 256 CUs, 0.28 s).  ``batches`` must be tensors
-        whose values are already in place (resident inputs, or host tensors); ``PleasFitter.steps`` must later be given
-        the same tensor objects first, in the same order.  Takes whole groups of ``group`` (default ``2 * world``) equal
-        batches, at most ``max_groups`` of them and as long as their taps (sized from the first group) fit into
-        ``memory_fraction`` of the HBM that is free or idle in the allocator's pools.  Returns the number of batches taken."""
-        if self._side_streams is None:
-            return 0
-        group = max(1, int(group or 2 * self.world))
-        batches = list(batches)
-        # The side streams skip the current stream's queue (the LAP kernel), but the memory they are about to take from
-        # their allocator pools may have been released by the host while its last readers are still queued: updates of an
-        # earlier fitter on the update stream (waited for here), matching kernels on model1's stream (in order with it;
-        # model2's stream follows model1's in run_eager).
-        self._side_streams[0].wait_stream(self.ops.role_stream(self.device, "updates"))
-        # what the taps may take: a share of the HBM that is free or sits unused in the caching allocator's pools
-        idle = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-        budget = (torch.cuda.mem_get_info(self.device)[0] + idle) * memory_fraction
-        per_group, taken = None, 0
-        for g in range(max_groups):
-            run = batches[g * group:(g + 1) * group]
-            if len(run) < group or any(not torch.is_tensor(b) or b.shape != run[0].shape or b.shape[0] == 0 for b in run):
-                break
-            if per_group is not None and (g + 1) * per_group > budget:
-                break
-            if group > 1:
-                self.launch_group(run, after_current=False)
-            else:
-                self.queue.append((run[0],) + self.launch(run[0], after_current=False))
-            taken += group
-            if per_group is None:      # bytes one group's taps hold (inputs and outputs of every hooked layer, both models)
-                gen = self.queue[-1]
-                per_group = 0
-                for taps in (gen[2][0], gen[2][1], gen[3][0], gen[3][1]):
-                    base = taps.base if isinstance(taps, _TapView) else taps
-                    per_group += sum(t.numel() * t.element_size() for t in base.values())
-        return taken
-
-    @torch.no_grad()
-    def run_eager(self, x: torch.Tensor, after_current: bool = True) -> None:
-        """Both source forwards (frozen: never under autograd), dispatched op by op; the hooks fill ``tap1`` / ``tap2`` (callers that read them right
-        away must synchronise: the models run on side streams).  ``after_current=False``: the side streams are not
-        ordered after the current stream's queue (``prefetch``); model2's stream then follows model1's up to here, which
-        is where the batch was put together."""
-        side = self._side_streams
-        if side is None:
-            with self.ops.pin_stream():
-                self.src1(x)
-                self.src2(x)
-            return
-        main = torch.cuda.current_stream(self.device)
-        # The sources' tensors live in the side streams' allocator pools.  They are consumed on `main` (by the update
-        # that owns this generation) and released by the host once that update is enqueued; a side stream re-uses them
-        # only after a LATER wait_stream(main), i.e. after every consumer enqueued on `main` up to then -- with one
-        # batch of look-ahead that is the update two generations back.  No record_stream bookkeeping needed.
-        events = []
-        if not after_current:          # model2's stream follows model1's up to HERE (the batch is in place), not its forward
-            here = torch.cuda.Event()
-            here.record(side[0])
-            side[1].wait_event(here)
-        for stream, model in zip(side, (self.src1, self.src2)):
-            if after_current:
-                stream.wait_stream(main)
-            with torch.cuda.stream(stream), self.ops.pin_stream():
-                model(x)
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            events.append(ev)
-        self._src_events = events
-
-    def close(self) -> None:
-        self.tap1.remove()
-        self.tap2.remove()
-        self.queue.clear()
-        self._staged.clear()
-
-
-class PleasFitter:
-    """State of one PLeaS run: flat arenas + per-layer plans.  ``train`` drives it; the bench
-    uses it directly to time single steps."""
+class _LayerFitter:
+    """What both solvers of the layer-wise objective share: the frozen sources, the flat parameter arena with its mask,
+    the per-layer plans, and the loop that hands one tap generation to ``_step`` per batch."""
 
     def __init__(self, model1, model2, model3, spec, perm, costs, budget_ratios, max_steps: int, lr: float = 5e-4,
                  separate_classifier=False, num_classes=1000, model_type="rn50", data_parallel: bool = False,
-                 fuse_sources: bool = True, overlap_sources: bool = True, fused_sources=None,
-                 sources: Optional[FrozenSources] = None, merging: str = "perm_gradmask",
-                 shard_optimizer: Optional[bool] = None):
-        from .. import hip_ops
-
+                 fuse_sources: bool = True, overlap_sources: bool = True, fused_sources=None, sources: Optional[FrozenSources] = None,
+                 merging: str = "perm_gradmask", shard_optimizer: Optional[bool] = None):
+        """``lr`` and ``shard_optimizer`` are Adam's (``PleasFitter``); the closed form accepts and ignores them."""
         self.ops = hip_ops
         # data parallel: every update splits the batch's samples over the ranks, gradients (one flat
         # arena) are summed with ONE all-reduce, so all ranks apply the same full-batch update
@@ -525,22 +192,12 @@ class PleasFitter:
         self.model1, self.model2, self.model3 = model1, model2, model3
         self.merging = merging_mode(merging)
         self.stacked = self.merging != "perm_gradmask"       # two half-batches per layer (reference :125-144)
-        blocks = get_blocks(spec, perm, costs, budget_ratios, False)
-        self.perm_blocks = spread_blocks(spec, blocks)
+        self.perm_blocks = spread_blocks(spec, get_blocks(spec, perm, costs, budget_ratios, False))
         # The update's own launches go to a dedicated stream, not to the caller's: measured on the 401-update job,
         # work on torch's default (null) stream overlaps the side streams markedly worse than work on a created stream
         # (8.24 s vs 7.73 s for the whole job).  step() orders that stream after the caller's and the caller's after it.
         self._upd_stream = hip_ops.role_stream(self.device, "updates") if self.sources._side_streams is not None else None
-        self._cur_x = None
-        self.t1_in = self.t1_out = self.t2_in = self.t2_out = None   # taps of the update being applied
-        # Per input shape: the merged inputs and residuals of every layer live in buffers that are kept between updates
-        # (written and read on the update stream only), so the item tables of the three grouped launches change between
-        # two updates of that shape in the tap addresses alone -- see _step.
-        self._buffers: Dict[tuple, Dict[tuple, Tuple[torch.Tensor, torch.Tensor]]] = {}
-        self._bufs: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}      # (layer, half-batch) -> (merged input, residual)
-        self._replay = None      # (shape key, names, merge table, forward table, bias work) of the latest full update
-        self.fast_updates = 0    # updates applied by patching the tables (the rest took the layer-by-layer path)
-
+        self.gen: Optional[Generation] = None      # what the update being applied reads: its batch and source taps
         layers = {n: m for n, m in model3.named_modules() if isinstance(m, (nn.Conv2d, nn.Linear))}
         # The grouped HIP kernels take dense, undilated Conv2d layers with a square kernel / stride / padding (and Linear
         # layers on 2-D inputs) -- every layer of the ResNets the reference loads.  Any other geometry (rectangular, dilated or
@@ -549,210 +206,73 @@ class PleasFitter:
         # an update that contains such a layer takes the layer-by-layer path every time ("Layer geometries").
         self.vendor_layers = [n for n, m in layers.items() if isinstance(m, nn.Conv2d) and not _square_conv(m)]
         self.layer_modules = layers
-        pad4 = lambda n: (n + 3) // 4 * 4   # every tensor starts 16-byte aligned inside the arenas (vector loads)
-        total = sum(pad4(p.numel()) for m in layers.values() for p in m.parameters())
-        # shard_optimizer (data parallel; default ON there since round 4, DESIGN.md section 5: the per-update exchange is as
-        # long as a rank's per-update compute, so nothing that does not shrink with the ranks may stay on the update's
-        # path): rank r keeps the Adam moments of -- and applies the update to -- the r-th
-        # 1/world slice of the flat arena only: reduce-scatter of the gradients, Adam on the slice, all-gather of the
-        # parameters.  Same bytes on the links as the all-reduce, 1/world of the optimiser's work and state per rank.
-        from .activation_matching import _force_collectives
-
-        if shard_optimizer is None:
-            shard_optimizer = True
-        self.shard_optimizer = bool(shard_optimizer) and (self.world > 1 or _force_collectives())
-        if self.shard_optimizer:
-            total = (total + 4 * self.world - 1) // (4 * self.world) * (4 * self.world)    # equal, 16-byte aligned slices
-        self._shard = total // self.world if self.shard_optimizer else total
-        dev = self.device
-        self.p = torch.zeros(total, dtype=torch.float32, device=dev)
-        # the gradient arena carries this update's per-layer losses in its tail: ONE collective per update sums both
-        self._g_ext = torch.zeros(total + len(layers), dtype=torch.float32, device=dev)
-        self.g = self._g_ext[:total]
-        # stacked modes: the second half-batch's weight gradients land in an arena of their own (two entries of one grouped
-        # launch must not write the same tensor) and are added before the exchange / the optimiser
-        self.g2 = torch.zeros(total, dtype=torch.float32, device=dev) if self.stacked else None
-        self.m = torch.zeros(self._shard, dtype=torch.float32, device=dev)     # this rank's slice only when sharded
-        self.v = torch.zeros(self._shard, dtype=torch.float32, device=dev)
-        self._g_shard = torch.zeros(self._shard, dtype=torch.float32, device=dev) if self.shard_optimizer else None
-        self.mask = torch.ones(total, dtype=torch.float32, device=dev)   # frozen blocks are zeroed in place below
+        self._lay_out_arenas(sum(_pad4(p.numel()) for m in layers.values() for p in m.parameters()), shard_optimizer)
         self.plans: List[_LayerPlan] = []
-        off, k = 0, 0
+        off = 0
         for name, mod in layers.items():
-            plan = _LayerPlan()
-            plan.name, plan.mod, plan.is_conv = name, mod, isinstance(mod, nn.Conv2d)
-            plan.vendor = name in self.vendor_layers
-            plan.b = plan.gb = plan.gw2 = plan.gb2 = None
-            # k x k convolutions with Cin % 32 == 0 keep their weight (gradient, mask, Adam state) KERNEL-POSITION-MAJOR
-            # [Cout][KH][KW][Cin] in the arenas: the fused forward then has one tap per K chunk, the weight-gradient
-            # kernel writes that layout directly, and the elementwise optimiser does not care (finish() permutes back)
-            plan.kpos = bool(plan.is_conv and _square_conv(mod) and mod.kernel_size[0] > 1
-                             and mod.weight.shape[1] % 32 == 0)   # the tensor's width: module attributes may be stale
-            for pname, prm in mod.named_parameters():
-                n = prm.numel()
-                kp = plan.kpos and pname == "weight"
-                shape = (prm.shape[0], prm.shape[2], prm.shape[3], prm.shape[1]) if kp else tuple(prm.shape)
-                # model3 may live on the host: move first, permute on the device (a strided copy of a 3x3 weight on the CPU
-                # costs milliseconds), and write the mask's frozen blocks straight into the arena
-                src = prm.detach().to(dev, non_blocking=True)
-                view, gview = self.p[off:off + n].view(shape), self.g[off:off + n].view(shape)
-                view.copy_(src.permute(0, 2, 3, 1) if kp else src)
-                if prm.dim() >= 2:
-                    mview = self.mask[off:off + n].view(shape)
-                    for rows, cols in _frozen_blocks(self.perm_blocks, name):
-                        if kp:
-                            mview[rows, :, :, cols] = 0.0
-                        else:
-                            mview[rows, cols] = 0.0
-                g2view = self.g2[off:off + n].view(shape) if self.stacked else None
-                if pname == "weight":
-                    plan.w, plan.gw, plan.w_shape, plan.off_w = view, gview, tuple(prm.shape), off
-                    plan.gw2 = g2view
-                else:
-                    plan.b, plan.gb = view, gview
-                    plan.gb2 = g2view
-                off += pad4(n)
-                k += 1
-            src = get_attr(model1, name.split("."))
-            cin = src.in_channels if plan.is_conv else src.in_features
-            bi = self.perm_blocks.get(Axis("%s.weight" % name, 1)) or _identity_block(cin)
-            bo = self.perm_blocks.get(Axis("%s.weight" % name, 0)) or _identity_block(
-                _fallback_out_width(separate_classifier, model_type, num_classes))
-            cout_src = src.out_channels if plan.is_conv else src.out_features
-            plan.halves = half_maps(self.merging, bi, bo, cin, cout_src, dev)
-            plan.in_maps, plan.out_maps = plan.halves[0]
-            self.plans.append(plan)
-        self.max_steps = max_steps
-        self.lrs = cosine_lrs(lr, max_steps, max_steps + 1)
-        self.step_count = 0
-        self.loss_now = self._g_ext[total:]                                             # this step, per layer
-        self.loss_sum = torch.zeros(len(self.plans), dtype=torch.float32, device=dev)   # since last report
-        self.wgrad = hip_ops.WgradBatch(dev)
-        self.fwd = hip_ops.FwdBatch(dev)
-        self.merge = hip_ops.MergeBatch(dev)
-        self._fwd_loss = None
-        self._fwd_index = None
+            off = self._plan_layer(name, mod, off, (separate_classifier, model_type, num_classes))
+        self.wgrad = hip_ops.WgradBatch(self.device)
+        self.merge = hip_ops.MergeBatch(self.device)
 
-    # the source side lives in `self.sources`; these names are what the loop (and the tests) use
-    tap1 = property(lambda self: self.sources.tap1)
-    tap2 = property(lambda self: self.sources.tap2)
-    src1 = property(lambda self: self.sources.src1)
-    src2 = property(lambda self: self.sources.src2)
-    _queue = property(lambda self: self.sources.queue)
-    _side_streams = property(lambda self: self.sources._side_streams)
+    def _lay_out_arenas(self, total: int, shard_optimizer: Optional[bool]) -> None:      # the flat arenas all layers' tensors are views of
+        self.p = torch.zeros(total, dtype=torch.float32, device=self.device)
+        self.mask = torch.ones(total, dtype=torch.float32, device=self.device)   # frozen blocks are zeroed in _plan_layer
 
-    @property
-    def _slice_batch(self):
-        return self.sources._slice_batch
-
-    @_slice_batch.setter
-    def _slice_batch(self, value):
-        self.sources._slice_batch = bool(value)
-
-    def _launch_sources(self, x: torch.Tensor, parts: int = 1):
-        return self.sources.launch(x, parts)
-
-    def _run_sources(self, x: torch.Tensor) -> None:
-        self.sources.run_eager(x)
-
-    # -- one layer: merged input; queue forward(+target+residual+loss) and weight gradient for the grouped launches
-    def _fit_layer(self, idx: int, plan: _LayerPlan) -> None:
-        ops = self.ops
-        name = plan.name
-        ip1, ip2 = self.t1_in[name], self.t2_in[name]
-        o1, o2 = self.t1_out[name], self.t2_out[name]
-        mod = plan.mod
-        cout = plan.w_shape[0]
-        square = plan.is_conv and _square_conv(mod)
-        linear = (not plan.is_conv) and ip1.dim() == 2
-        if not (square or linear):
-            self._fit_layer_vendor(idx, plan)
-            return
-        geo = (tuple(mod.kernel_size), mod.stride[0], mod.padding[0]) if plan.is_conv else ((1, 1), 1, 0)
-        # a 1x1 convolution with a stride reads every s-th pixel of every s-th line: the grouped merge writes exactly those, and
-        # the layer is a dense 1x1 stride-1 layer for the forward and the weight gradient (16-byte loads along the pixel axis
-        # instead of 4-byte loads at a stride; ResNet-101's three downsample layers: 52 -> ~100 TFLOP/s in the grouped forward)
-        sub = geo[1] if (plan.is_conv and geo[0] == (1, 1) and geo[1] > 1 and geo[2] == 0) else 1
-        if sub > 1:
-            geo = ((1, 1), 1, 0)
-        halves = len(plan.halves)
-        for h, (in_maps, (r1, r2, nm)) in enumerate(plan.halves):
-            if cout != r1.numel():
-                raise RuntimeError("layer %s: %d merged outputs vs %d target blocks" % (name, cout, r1.numel()))
-            if in_maps[0].numel() != plan.w_shape[1]:
-                raise RuntimeError("layer %s: %d merged inputs vs %d input blocks" % (name, plan.w_shape[1], in_maps[0].numel()))
-            # merged input: queued for the ONE grouped merge launch that precedes the grouped forward (merge.flush)
-            kept = self._bufs.get((idx, h))
-            ip = self.merge.add(ip1, ip2, 1, *in_maps, out=kept[0] if kept else None, subsample=sub)
-            resid = kept[1] if kept else torch.empty((ip.shape[0], cout) + tuple(o1.shape[2:]), dtype=torch.float32,
-                                                     device=ip.device)
-            if kept is None:
-                self._bufs[(idx, h)] = (ip, resid)
-            n = resid.numel() * halves * self.world    # the mean runs over the full (global, stacked) batch
-            self.fwd.add(ip, plan.w, plan.b, o1, o2, r1, r2, nm, resid, 2.0 / n, 1.0 / n, *geo,
-                         flags=ops.FwdBatch.KPOS_MAJOR if plan.kpos else 0)
-            self._fwd_rows.append(idx)
-            gw, gb = (plan.gw, plan.gb) if h == 0 else (plan.gw2, plan.gb2)   # second half: its own arena, added in _step
-            # every layer, the 3-channel stem included (its rows are (channel, tap) pairs: "virtual channels", csrc/conv.hip)
-            self.wgrad.add(resid, ip, gw, *geo, flags=ops.WgradBatch.KPOS_MAJOR if plan.kpos else 0)
-            if gb is not None:
-                self._bias_grads.append((resid, plan, gb))
-
-    def _fit_layer_vendor(self, idx: int, plan: _LayerPlan) -> None:
-        """A layer the grouped kernels do not take, fitted as the reference fits every layer (pleas_merging.py:116-147, :281-287):
-        merged input and target by ``pleas_merge_blocks``, then ``layer(ip)``, the MSE and its gradients on the vendor's operators
-        under autograd.  Gradients land in the same arena (mask and Adam are shared with all other layers); the loss joins
-        ``loss_now`` after the grouped forward's."""
-        import torch.nn.functional as F
-
-        ops, name, mod = self.ops, plan.name, plan.mod
-        ip1, ip2 = self.t1_in[name], self.t2_in[name]
-        o1, o2 = self.t1_out[name], self.t2_out[name]
-        halves = len(plan.halves)
-        for h, (in_maps, out_maps) in enumerate(plan.halves):
-            axis = 1 if plan.is_conv else ip1.dim() - 1      # channels: axis 1 of a feature map, the last axis of a Linear input
-            ip = ops.merge_blocks(ip1, ip2, axis, *in_maps)
-            op = ops.merge_blocks(o1, o2, axis, *out_maps)
-            with torch.enable_grad():
-                w = plan.w.detach().requires_grad_(True)
-                b = plan.b.detach().requires_grad_(True) if plan.b is not None else None
-                if plan.is_conv:
-                    out = F.conv2d(ip, w, b, mod.stride, mod.padding, mod.dilation, mod.groups)
-                else:
-                    out = F.linear(ip, w, b)
-                n = out.numel() * halves * self.world      # the mean runs over the full (global, stacked) batch
-                loss = ((out - op) ** 2).sum() / n
-                grads = torch.autograd.grad(loss, [w] + ([b] if b is not None else []))
-            gw, gb = (plan.gw, plan.gb) if h == 0 else (plan.gw2, plan.gb2)
-            gw.copy_(grads[0])
-            if b is not None:
-                gb.copy_(grads[1])
-            self._vendor_losses.append((idx, loss.detach()))
-        self._complete = False      # no table to replay: the next update goes layer by layer again
-
-    def _bias_gradients(self) -> None:
-        for resid, plan, gb in self._bias_grads:      # HIP: one deterministic row-sum launch per biased layer
-            self.ops.channel_sum(resid if resid.dim() > 1 else resid.reshape(1, -1), gb)
+    def _plan_layer(self, name: str, mod: nn.Module, off: int, fallback: tuple) -> int:
+        """Plan of one layer: its parameters copied into the arena from ``off`` on (returns where the next layer starts),
+        its frozen blocks zeroed in the mask, and the block maps of its regression problem."""
+        plan, dev = _LayerPlan(), self.device
+        plan.name, plan.mod, plan.is_conv = name, mod, isinstance(mod, nn.Conv2d)
+        plan.b = plan.gw = plan.gb = plan.gw2 = plan.gb2 = None
+        # k x k convolutions with Cin % 32 == 0 keep their weight (gradient, mask, Adam state) KERNEL-POSITION-MAJOR
+        # [Cout][KH][KW][Cin] in the arenas: the fused forward then has one tap per K chunk, the weight-gradient
+        # kernel writes that layout directly, and the elementwise optimiser does not care (finish() permutes back)
+        plan.kpos = bool(plan.is_conv and _square_conv(mod) and mod.kernel_size[0] > 1
+                         and mod.weight.shape[1] % 32 == 0)   # the tensor's width: module attributes may be stale
+        for pname, prm in mod.named_parameters():
+            n = prm.numel()
+            kp = plan.kpos and pname == "weight"
+            shape = (prm.shape[0], prm.shape[2], prm.shape[3], prm.shape[1]) if kp else tuple(prm.shape)
+            # model3 may live on the host: move first, permute on the device (a strided copy of a 3x3 weight on the CPU
+            # costs milliseconds), and write the mask's frozen blocks straight into the arena
+            src = prm.detach().to(dev, non_blocking=True)
+            view = self.p[off:off + n].view(shape)
+            view.copy_(src.permute(0, 2, 3, 1) if kp else src)
+            if prm.dim() >= 2:
+                mview = self.mask[off:off + n].view(shape)
+                for rows, cols in _frozen_blocks(self.perm_blocks, name):
+                    mview[(rows, slice(None), slice(None), cols) if kp else (rows, cols)] = 0.0
+            if pname == "weight":
+                plan.w, plan.w_shape, plan.off_w = view, tuple(prm.shape), off
+            else:
+                plan.b = view
+            off += _pad4(n)
+        src = get_attr(self.model1, name.split("."))
+        cin = src.in_channels if plan.is_conv else src.in_features
+        bi = self.perm_blocks.get(Axis("%s.weight" % name, 1)) or _identity_block(cin)
+        bo = self.perm_blocks.get(Axis("%s.weight" % name, 0)) or _identity_block(_fallback_out_width(*fallback))
+        cout_src = src.out_channels if plan.is_conv else src.out_features
+        plan.halves = half_maps(self.merging, bi, bo, cin, cout_src, dev)
+        self.plans.append(plan)
+        return off
 
     def _begin_update(self, x: torch.Tensor, next_x: Optional[torch.Tensor]) -> None:
         """Taps of ``x`` become current (running its sources now unless they were prefetched); the sources of
         ``next_x`` are enqueued BEFORE this update's own kernels, so that they overlap them on the side streams."""
-        if self._queue and self._queue[0][0] is not x:
+        sources, queue = self.sources, self.sources.queue
+        if queue and queue[0].batch is not x:
             raise RuntimeError("PleasFitter.step: a different batch was prefetched than the one passed now")
-        cur = self._queue.popleft() if self._queue else (x,) + self._launch_sources(x)
-        if next_x is not None and not self._queue and self._side_streams is not None:
-            self._queue.append((next_x,) + self._launch_sources(next_x))
-        _, self._cur_x, (self.t1_in, self.t1_out), (self.t2_in, self.t2_out), events = cur
-        if events is not None:
-            main = torch.cuda.current_stream(self.device)
-            for ev in events:
-                main.wait_event(ev)
+        self.gen = queue.popleft() if queue else Generation(x, sources.launch(x))
+        if next_x is not None and not queue and sources._side_streams is not None:
+            sources.enqueue(next_x)
+        main = torch.cuda.current_stream(self.device)
+        for ev in self.gen.taps.events or ():
+            main.wait_event(ev)
 
     def _end_update(self) -> None:
         # the device copy of the batch was read on the side streams: it is released only now, after this update's
         # kernels (which waited for those streams) are enqueued on the stream that owns its memory
-        self._cur_x = None
-        self.t1_in = self.t1_out = self.t2_in = self.t2_out = None
+        self.gen = None
 
     @contextlib.contextmanager
     def _session(self):
@@ -793,15 +313,14 @@ class PleasFitter:
         shares the CUs (fused forward 2.9 -> 4.3 ms per launch), so it is off there and per-kernel timings stay
         interpretable.  Under data parallelism (the default then) the stream that applies the updates idles during every
         gradient all-reduce, and the prefetched source forwards are what fills those gaps."""
-        if sources_per_forward is None:
-            sources_per_forward = 2 * self.world
-        group = max(1, int(sources_per_forward))
+        group = max(1, int(2 * self.world if sources_per_forward is None else sources_per_forward))
         if lookahead is None:
             lookahead = self.world > 1
         keep = group if lookahead else 0      # sources are launched whenever no more than `keep` generations are queued
+        sources, queue = self.sources, self.sources.queue
         it = iter(batches)
-        for gen in list(self._queue):         # forwards enqueued beforehand (FrozenSources.prefetch): same batches first
-            if next(it, None) is not gen[0]:
+        for gen in list(queue):               # forwards enqueued beforehand (FrozenSources.prefetch): same batches first
+            if next(it, None) is not gen.batch:
                 raise RuntimeError("PleasFitter.steps: the prefetched batches must be the first ones, in order")
         ahead: List[torch.Tensor] = []        # fetched from `it`, sources not launched yet
         exhausted = False
@@ -811,7 +330,7 @@ class PleasFitter:
             # per update, so a consumer that breaks out of (or raises inside) the loop is on its own stream, ordered after
             # the updates it has seen -- nothing is left to a generator's finalisation.
             with self._session():
-                while len(self._queue) <= keep:
+                while len(queue) <= keep:
                     while len(ahead) < 2 * group and not exhausted:      # one group to launch, one whose copies start now
                         nxt = next(it, None)
                         if nxt is None:
@@ -829,15 +348,14 @@ class PleasFitter:
                     if group > 1 and (len(run) == group or (exhausted and len(run) > 1 and len(run) == len(ahead))):
                         # a full group -- or, when the batches have run out, what is left of one (one more forward size,
                         # instead of one forward per left-over batch)
-                        self.sources.launch_group(run)      # one generation per batch of the run
+                        sources.launch_group(run)      # one generation per batch of the run
                         del ahead[:len(run)]
                     else:
-                        b = ahead.pop(0)
-                        self._queue.append((b,) + self._launch_sources(b))
-                    self.sources.stage(ahead[:group])
-                if not self._queue:
+                        sources.enqueue(ahead.pop(0))
+                    sources.stage(ahead[:group])
+                if not queue:
                     break
-                self.step(self._queue[0][0])
+                self.step(queue[0].batch)
             yield idx
             idx += 1
 
@@ -845,88 +363,248 @@ class PleasFitter:
     def step(self, x: torch.Tensor, next_x: Optional[torch.Tensor] = None) -> None:
         """One update: reference ``step`` (:234-302) + ``lr_sched.step()`` (:375).  ``next_x`` (optional): the batch
         of the NEXT call; its source forwards are enqueued now and run beside this update.  On return the work is
-        ordered before anything enqueued later on the caller's stream."""
+        ordered before anything enqueued later on the caller's stream.  ``_step`` is the solver's: it begins with
+        ``_begin_update`` and ends with ``_end_update``."""
         with self._session():
             self._step(x, next_x)
 
+    def finish(self) -> nn.Module:
+        """Write the fitted weights back into ``model3`` and drop the hooks (reference :392-403)."""
+        sd = self.model3.state_dict()
+        for plan in self.plans:
+            sd["%s.weight" % plan.name] = (plan.w.detach().permute(0, 3, 1, 2) if plan.kpos else plan.w.detach()).clone()
+            if plan.b is not None:
+                sd["%s.bias" % plan.name] = plan.b.detach().clone()
+        self.model3.load_state_dict(sd)
+        self.sources.close()
+        return self.model3
+
+
+class _UpdateRecord:
+    """What the layer-by-layer path of ONE update set up, and all that a later update of the same input shape needs in order
+    to repeat it with other tap addresses.  ``_fit_layer`` / ``_fit_layer_vendor`` write here; ``_replay_update`` reads
+    nothing else."""
+
+    __slots__ = ("key", "bufs", "names", "fwd_rows", "fwd_loss", "fwd_index", "bias_grads", "vendor_losses", "merge_tab", "fwd_tab", "complete")
+
+    def __init__(self, key: tuple, bufs: dict):
+        self.key, self.bufs = key, bufs    # input shape (_update_key); (layer, half-batch) -> (merged input, residual) of that shape
+        # per entry of the grouped forward its plan's index; (residual, plan, bias gradient); vendor layers' (plan index, loss)
+        self.fwd_rows, self.bias_grads, self.vendor_losses = [], [], []
+        self.names = self.fwd_loss = self.fwd_index = self.merge_tab = self.fwd_tab = None
+        self.complete = bool(key)          # replayable: every layer went through the grouped launches and their tables agree
+
+
+class PleasFitter(_LayerFitter):
+    """State of one PLeaS run: flat arenas + per-layer plans.  ``train`` drives it; the bench uses it directly to time single steps."""
+
+    def __init__(self, model1, model2, model3, spec, perm, costs, budget_ratios, max_steps: int, lr: float = 5e-4, *args, **kwargs):
+        super().__init__(model1, model2, model3, spec, perm, costs, budget_ratios, max_steps, lr, *args, **kwargs)
+        # per-plan gradients: the views of the gradient arenas at the place the parameter has in `p`
+        like = lambda arena, t: None if arena is None or t is None else \
+            arena[t.storage_offset():t.storage_offset() + t.numel()].view(t.shape)
+        for plan in self.plans:
+            plan.gw, plan.gb, plan.gw2, plan.gb2 = like(self.g, plan.w), like(self.g, plan.b), like(self.g2, plan.w), like(self.g2, plan.b)
+        self.lrs = cosine_lrs(lr, max_steps, max_steps + 1)
+        self.step_count = 0
+        self.loss_now = self._g_ext[self.p.numel():]                                             # this step, per layer
+        self.loss_sum = torch.zeros(len(self.plans), dtype=torch.float32, device=self.device)   # since last report
+        self.fwd = self.ops.FwdBatch(self.device)
+        # Per input shape: the merged inputs and residuals of every layer live in buffers that are kept between updates
+        # (written and read on the update stream only), so the item tables of the three grouped launches change between
+        # two updates of that shape in the tap addresses alone -- see _step.
+        self._buffers: Dict[tuple, Dict[tuple, Tuple[torch.Tensor, torch.Tensor]]] = {}
+        self._loss_bufs: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}    # forward rows -> (their losses, their plan indices)
+        self._replay: Optional[_UpdateRecord] = None      # the latest update's record, if complete
+        self.fast_updates = 0    # updates applied by patching the tables (the rest took the layer-by-layer path)
+
+    def _lay_out_arenas(self, total: int, shard_optimizer: Optional[bool]) -> None:
+        # shard_optimizer (data parallel; default ON there since round 4, DESIGN.md section 5: the per-update exchange is as
+        # long as a rank's per-update compute, so nothing that does not shrink with the ranks may stay on the update's
+        # path): rank r keeps the Adam moments of -- and applies the update to -- the r-th
+        # 1/world slice of the flat arena only: reduce-scatter of the gradients, Adam on the slice, all-gather of the
+        # parameters.  Same bytes on the links as the all-reduce, 1/world of the optimiser's work and state per rank.
+        self.shard_optimizer = (shard_optimizer is None or bool(shard_optimizer)) and (self.world > 1 or _force_collectives())
+        if self.shard_optimizer:
+            total = (total + 4 * self.world - 1) // (4 * self.world) * (4 * self.world)    # equal, 16-byte aligned slices
+        self._shard = total // self.world if self.shard_optimizer else total
+        super()._lay_out_arenas(total, shard_optimizer)
+        dev = self.device
+        # the gradient arena carries this update's per-layer losses in its tail: ONE collective per update sums both
+        self._g_ext = torch.zeros(total + len(self.layer_modules), dtype=torch.float32, device=dev)
+        self.g = self._g_ext[:total]
+        # stacked modes: the second half-batch's weight gradients land in an arena of their own (two entries of one grouped
+        # launch must not write the same tensor) and are added before the exchange / the optimiser
+        self.g2 = torch.zeros(total, dtype=torch.float32, device=dev) if self.stacked else None
+        self.m = torch.zeros(self._shard, dtype=torch.float32, device=dev)     # this rank's slice only when sharded
+        self.v = torch.zeros(self._shard, dtype=torch.float32, device=dev)
+        self._g_shard = torch.zeros(self._shard, dtype=torch.float32, device=dev) if self.shard_optimizer else None
+
+    # -- one layer: merged input; queue forward(+target+residual+loss) and weight gradient for the grouped launches
+    def _fit_layer(self, idx: int, plan: _LayerPlan, rec: _UpdateRecord) -> None:
+        ops, name, mod, cout = self.ops, plan.name, plan.mod, plan.w_shape[0]
+        ip1, ip2 = (t[name] for t in self.gen.taps.inputs)
+        o1, o2 = (t[name] for t in self.gen.taps.outputs)
+        if not (_square_conv(mod) if plan.is_conv else ip1.dim() == 2):
+            self._fit_layer_vendor(idx, plan, rec)
+            return
+        geo = (tuple(mod.kernel_size), mod.stride[0], mod.padding[0]) if plan.is_conv else ((1, 1), 1, 0)
+        # a 1x1 convolution with a stride reads every s-th pixel of every s-th line: the grouped merge writes exactly those, and
+        # the layer is a dense 1x1 stride-1 layer for the forward and the weight gradient (16-byte loads along the pixel axis
+        # instead of 4-byte loads at a stride; ResNet-101's three downsample layers: 52 -> ~100 TFLOP/s in the grouped forward)
+        sub = geo[1] if (plan.is_conv and geo[0] == (1, 1) and geo[1] > 1 and geo[2] == 0) else 1
+        if sub > 1:
+            geo = ((1, 1), 1, 0)
+        for h, (in_maps, (r1, r2, nm)) in enumerate(plan.halves):
+            if cout != r1.numel():
+                raise RuntimeError("layer %s: %d merged outputs vs %d target blocks" % (name, cout, r1.numel()))
+            if in_maps[0].numel() != plan.w_shape[1]:
+                raise RuntimeError("layer %s: %d merged inputs vs %d input blocks" % (name, plan.w_shape[1], in_maps[0].numel()))
+            # merged input: queued for the ONE grouped merge launch that precedes the grouped forward (merge.flush)
+            kept = rec.bufs.get((idx, h))
+            ip = self.merge.add(ip1, ip2, 1, *in_maps, out=kept[0] if kept else None, subsample=sub)
+            resid = kept[1] if kept else torch.empty((ip.shape[0], cout) + tuple(o1.shape[2:]), dtype=torch.float32,
+                                                     device=ip.device)
+            if kept is None:
+                rec.bufs[(idx, h)] = (ip, resid)
+            n = resid.numel() * len(plan.halves) * self.world    # the mean runs over the full (global, stacked) batch
+            self.fwd.add(ip, plan.w, plan.b, o1, o2, r1, r2, nm, resid, 2.0 / n, 1.0 / n, *geo,
+                         flags=ops.FwdBatch.KPOS_MAJOR if plan.kpos else 0)
+            rec.fwd_rows.append(idx)
+            gw, gb = (plan.gw, plan.gb) if h == 0 else (plan.gw2, plan.gb2)   # second half: its own arena, added before the exchange
+            # every layer, the 3-channel stem included (its rows are (channel, tap) pairs: "virtual channels", csrc/conv.hip)
+            self.wgrad.add(resid, ip, gw, *geo, flags=ops.WgradBatch.KPOS_MAJOR if plan.kpos else 0)
+            if gb is not None:
+                rec.bias_grads.append((resid, plan, gb))
+
+    def _fit_layer_vendor(self, idx: int, plan: _LayerPlan, rec: _UpdateRecord) -> None:
+        """A layer the grouped kernels do not take, fitted as the reference fits every layer (pleas_merging.py:116-147, :281-287):
+        merged input and target by ``pleas_merge_blocks``, then ``layer(ip)``, the MSE and its gradients on the vendor's operators
+        under autograd.  Gradients land in the same arena (mask and Adam are shared with all other layers); the loss joins
+        ``loss_now`` after the grouped forward's."""
+        ops, name, mod = self.ops, plan.name, plan.mod
+        ip1, ip2 = (t[name] for t in self.gen.taps.inputs)
+        o1, o2 = (t[name] for t in self.gen.taps.outputs)
+        for h, (in_maps, out_maps) in enumerate(plan.halves):
+            axis = 1 if plan.is_conv else ip1.dim() - 1      # channels: axis 1 of a feature map, the last axis of a Linear input
+            ip = ops.merge_blocks(ip1, ip2, axis, *in_maps)
+            op = ops.merge_blocks(o1, o2, axis, *out_maps)
+            with torch.enable_grad():
+                w = plan.w.detach().requires_grad_(True)
+                b = plan.b.detach().requires_grad_(True) if plan.b is not None else None
+                if plan.is_conv:
+                    out = F.conv2d(ip, w, b, mod.stride, mod.padding, mod.dilation, mod.groups)
+                else:
+                    out = F.linear(ip, w, b)
+                n = out.numel() * len(plan.halves) * self.world      # the mean runs over the full (global, stacked) batch
+                loss = ((out - op) ** 2).sum() / n
+                grads = torch.autograd.grad(loss, [w] + ([b] if b is not None else []))
+            gw, gb = (plan.gw, plan.gb) if h == 0 else (plan.gw2, plan.gb2)
+            gw.copy_(grads[0])
+            if b is not None:
+                gb.copy_(grads[1])
+            rec.vendor_losses.append((idx, loss.detach()))
+        rec.complete = False      # no table to replay: the next update goes layer by layer again
+
+    def _bias_gradients(self, rec: _UpdateRecord) -> None:
+        for resid, plan, gb in rec.bias_grads:      # HIP: one deterministic row-sum launch per biased layer
+            self.ops.channel_sum(resid if resid.dim() > 1 else resid.reshape(1, -1), gb)
+
     def _update_key(self) -> tuple:
-        first = self.plans[0].name
-        if first not in self.t1_in:
+        first, taps = self.plans[0].name, self.gen.taps.taps1[0]
+        if first not in taps:
             return ()
-        taps = self.t1_in
         n = (taps.hi - taps.lo) if isinstance(taps, _TapView) else taps[first].shape[0]
-        return (n,) + tuple(self._cur_x.shape[1:])
+        return (n,) + tuple(self.gen.taps.x.shape[1:])
 
     def _step(self, x: torch.Tensor, next_x: Optional[torch.Tensor]) -> None:
-        """One update.  The first update of an input shape goes layer by layer (_fit_layer: checks, buffers, item tables of
-        the three grouped launches).  Every further update of that shape differs from it in the addresses of the source
+        """One update.  The first update of an input shape goes layer by layer (_record_update: checks, buffers, item tables
+        of the three grouped launches).  Every further update of that shape differs from it in the addresses of the source
         taps alone, so it rewrites those four pointer columns (numpy, from one address table per source forward) and
-        launches again: ~2.3 ms -> ~0.5 ms of host time per update, which is what bounds a rank once its share of an update
-        is a few samples."""
+        launches again (_replay_update): ~2.3 ms -> ~0.5 ms of host time per update, which is what bounds a rank once its
+        share of an update is a few samples."""
         self._begin_update(x, next_x)
         key = self._update_key()
-        replay = self._replay if (self._replay is not None and key and self._replay[0] == key) else None
+        rec = self._replay if (self._replay is not None and key and self._replay.key == key) else None
         ptrs = None
-        if replay is not None:
-            names = replay[1]
-            ptrs = [tap_pointers(t, names) for t in (self.t1_in, self.t2_in, self.t1_out, self.t2_out)]
+        if rec is not None:
+            ptrs = [tap_pointers(t, rec.names) for t in self.gen.taps.inputs + self.gen.taps.outputs]
             if any(p is None for p in ptrs):
-                replay = None
-        if replay is not None:
-            _, names, merge_tab, fwd_tab, self._bias_grads = replay
-            merge_tab["w1"][:], merge_tab["w2"][:], fwd_tab["o1"][:], fwd_tab["o2"][:] = ptrs
-            with self.ops.pin_stream():
-                self.merge.relaunch()
-                self.fwd.relaunch(self._fwd_loss)
-            self.fast_updates += 1
+                rec = None
+        if rec is not None:
+            self._replay_update(rec, ptrs)
         else:
             self._replay = None
-            self._bufs = self._buffers.setdefault(key, {}) if key else {}
-            self._fwd_rows, self._bias_grads = [], []
-            self._vendor_losses, self._complete = [], True
-            complete = bool(key)
-            with self.ops.pin_stream():
-                for idx, plan in enumerate(self.plans):
-                    if plan.name not in self.t1_in or plan.name not in self.t2_in:
-                        print("Key error on %s" % plan.name)
-                        complete = False
-                        continue
-                    self._fit_layer(idx, plan)
-            complete = complete and self._complete
-            self.merge.flush()   # ONE grouped launch: the merged inputs of every layer
-            if self._fwd_rows:   # ONE grouped MFMA launch: forward + target + residual + loss of every merged layer
-                if self._fwd_loss is None or self._fwd_loss.numel() != len(self._fwd_rows):
-                    self._fwd_loss = torch.zeros(len(self._fwd_rows), dtype=torch.float32, device=self.device)
-                    self._fwd_index = torch.tensor(self._fwd_rows, dtype=torch.long, device=self.device)
-                self.fwd.flush(self._fwd_loss)
-        if self._fwd_rows:
+            rec = self._record_update(key)
+            if rec.complete:
+                self._replay = rec
+        self._exchange_and_apply()
+        self._end_update()
+
+    def _record_update(self, key: tuple) -> _UpdateRecord:
+        """The layer-by-layer path: every layer's entries, the three grouped launches, the record of what was launched."""
+        rec = _UpdateRecord(key, self._buffers.setdefault(key, {}) if key else {})
+        in1, in2 = self.gen.taps.inputs
+        with self.ops.pin_stream():
+            for idx, plan in enumerate(self.plans):
+                if plan.name not in in1 or plan.name not in in2:
+                    print("Key error on %s" % plan.name)
+                    rec.complete = False
+                    continue
+                self._fit_layer(idx, plan, rec)
+        self.merge.flush()   # ONE grouped launch: the merged inputs of every layer
+        if rec.fwd_rows:     # ONE grouped MFMA launch: forward + target + residual + loss of every merged layer
+            rows = tuple(rec.fwd_rows)
+            if rows not in self._loss_bufs:
+                self._loss_bufs[rows] = (torch.zeros(len(rows), dtype=torch.float32, device=self.device),
+                                         torch.tensor(rows, dtype=torch.long, device=self.device))
+            rec.fwd_loss, rec.fwd_index = self._loss_bufs[rows]
+            self.fwd.flush(rec.fwd_loss)
+        self._scatter_losses(rec)
+        self._bias_gradients(rec)
+        n_wgrad = self.wgrad.pending()
+        self.wgrad.flush()   # ONE grouped MFMA launch: weight gradients of every merged layer
+        rec.complete = rec.complete and n_wgrad > 0
+        if rec.complete:
+            rec.names = tuple(self.plans[i].name for i in rec.fwd_rows)
+            rec.merge_tab, rec.fwd_tab = self.merge.table(), self.fwd.table()
+            rec.complete = (rec.merge_tab is not None and rec.fwd_tab is not None
+                            and len(rec.merge_tab) == len(rec.fwd_tab) == len(rec.names))
+        return rec
+
+    def _replay_update(self, rec: _UpdateRecord, ptrs: list) -> None:
+        """The recorded launches again on this update's taps: ``ptrs`` = addresses of both models' inputs, then of their outputs."""
+        rec.merge_tab["w1"][:], rec.merge_tab["w2"][:], rec.fwd_tab["o1"][:], rec.fwd_tab["o2"][:] = ptrs
+        with self.ops.pin_stream():
+            self.merge.relaunch()
+            self.fwd.relaunch(rec.fwd_loss)
+        self.fast_updates += 1
+        self._scatter_losses(rec)
+        self._bias_gradients(rec)
+        with self.ops.pin_stream():
+            self.wgrad.relaunch()
+
+    def _scatter_losses(self, rec: _UpdateRecord) -> None:
+        """Per-layer losses of this update into ``loss_now`` (the gradient arena's tail)."""
+        if rec.fwd_rows:
             if self.stacked:        # two entries (half-batches) per layer: their losses add up
                 self.loss_now.zero_()
-                self.loss_now.index_add_(0, self._fwd_index, self._fwd_loss)
+                self.loss_now.index_add_(0, rec.fwd_index, rec.fwd_loss)
             else:
-                self.loss_now.index_copy_(0, self._fwd_index, self._fwd_loss)
-        if replay is None and self._vendor_losses:      # layers fitted on the vendor's operators (_fit_layer_vendor)
-            if not self._fwd_rows:
+                self.loss_now.index_copy_(0, rec.fwd_index, rec.fwd_loss)
+        if rec.vendor_losses:       # layers fitted on the vendor's operators (_fit_layer_vendor)
+            if not rec.fwd_rows:
                 self.loss_now.zero_()
             seen = set()
-            for idx, loss in self._vendor_losses:
+            for idx, loss in rec.vendor_losses:
                 if idx in seen:
                     self.loss_now[idx] += loss
                 else:
                     self.loss_now[idx] = loss
                     seen.add(idx)
-        self._bias_gradients()
-        if replay is not None:
-            with self.ops.pin_stream():
-                self.wgrad.relaunch()
-        else:
-            n_wgrad = self.wgrad.pending()
-            self.wgrad.flush()  # ONE grouped MFMA launch: weight gradients of every merged layer
-            if complete and n_wgrad > 0:
-                names = tuple(self.plans[i].name for i in self._fwd_rows)
-                merge_tab, fwd_tab = self.merge.table(), self.fwd.table()
-                if merge_tab is not None and fwd_tab is not None and len(merge_tab) == len(fwd_tab) == len(names):
-                    self._replay = (key, names, merge_tab, fwd_tab, self._bias_grads)
+
+    def _exchange_and_apply(self) -> None:
+        """Gradients (and losses) summed over the ranks, then ONE masked Adam launch -- on this rank's slice when sharded."""
         if self.stacked:
             self.g.add_(self.g2)     # second half-batch's gradients (same launch, own arena)
         lr = self.lrs[min(self.step_count, len(self.lrs) - 1)]
@@ -942,18 +620,6 @@ class PleasFitter:
             dp_sum_(self._g_ext, self.world)     # gradients + losses: ONE collective per update
             self.loss_sum.add_(self.loss_now)
             self.ops.masked_adam(self.p, self.g, self.mask, self.m, self.v, lr, self.step_count)
-        self._end_update()
-
-    def finish(self) -> nn.Module:
-        """Write the fitted weights back into ``model3`` and drop the hooks (reference :392-403)."""
-        sd = self.model3.state_dict()
-        for plan in self.plans:
-            sd["%s.weight" % plan.name] = (plan.w.detach().permute(0, 3, 1, 2) if plan.kpos else plan.w.detach()).clone()
-            if plan.b is not None:
-                sd["%s.bias" % plan.name] = plan.b.detach().clone()
-        self.model3.load_state_dict(sd)
-        self.sources.close()
-        return self.model3
 
 
 def train(dataloader, model1, model2, model3, spec, perm, costs, budget_ratios, WANDB, MAX_STEPS, wandb_run,
@@ -973,7 +639,6 @@ def train(dataloader, model1, model2, model3, spec, perm, costs, budget_ratios, 
         raise ValueError("solver must be 'adam' or 'normal_eq'")
     fit = PleasFitter(model1, model2, model3, spec, perm, costs, budget_ratios, MAX_STEPS, lr, separate_classifier,
                       num_classes, model_type, merging=merging)
-    names = [p.name for p in fit.plans]
 
     def inputs():
         for idx, batch in enumerate(dataloader):
@@ -989,7 +654,7 @@ def train(dataloader, model1, model2, model3, spec, perm, costs, budget_ratios, 
             total = float(per_layer.sum())
             print("Loss: %.3f" % total)
             if WANDB:
-                metrics = {"loss_%s" % n: float(v) for n, v in zip(names, per_layer)}
+                metrics = {"loss_%s" % p.name: float(v) for p, v in zip(fit.plans, per_layer)}
                 metrics["step"], metrics["loss"] = idx, total
                 wandb_run.log(metrics)
             fit.loss_sum.zero_()

@@ -29,7 +29,8 @@ def check_update_against_fp64(fit, m3, spec, perm, costs_cpu, ratios, x, num_cla
     kept, release = {}, fit._end_update
 
     def keep_taps():        # the very tensors this update read (a second source forward may pick other vendor algorithms)
-        kept.update(i1=fit.t1_in, i2=fit.t2_in, o1=fit.t1_out, o2=fit.t2_out)
+        (i1, i2), (o1, o2) = fit.gen.taps.inputs, fit.gen.taps.outputs
+        kept.update(i1=i1, i2=i2, o1=o1, o2=o2)
         release()
 
     fit._end_update = keep_taps

@@ -461,12 +461,13 @@ def test_fused_source_forwards_match_module_forwards(tiny_bottleneck):
     for fuse in (False, True):
         m3 = partial_merge(t.spec, m1, m2, perm, costs, 0.5)
         fit = PleasFitter(m1, m2, m3, t.spec, perm, costs, 0.5, 3, num_classes=10, fuse_sources=fuse)
-        assert (fit.src1 is not m1) == fuse and (fit.src2 is not m2) == fuse
-        fit._run_sources(data[0][0].cuda())
+        src = fit.sources
+        assert (src.src1 is not m1) == fuse and (src.src2 is not m2) == fuse
+        src.run_eager(data[0][0].cuda())
         torch.cuda.synchronize()   # the sources run on side streams
-        taps.append(({k: v.clone() for k, v in fit.tap1.inputs.items()}, {k: v.clone() for k, v in fit.tap2.outputs.items()}))
-        fit.tap1.clear()
-        fit.tap2.clear()
+        taps.append(({k: v.clone() for k, v in src.tap1.inputs.items()}, {k: v.clone() for k, v in src.tap2.outputs.items()}))
+        src.tap1.clear()
+        src.tap2.clear()
         for x, _ in data:
             fit.step(x)
         outs.append({k: v.clone() for k, v in fit.finish().state_dict().items()})
@@ -495,7 +496,7 @@ def test_two_stream_source_forwards_equal_single_stream(tiny_bottleneck):
     for overlap in (False, True):
         m3 = partial_merge(t.spec, m1, m2, perm, costs, 0.5)
         fit = PleasFitter(m1, m2, m3, t.spec, perm, costs, 0.5, 7, num_classes=10, overlap_sources=overlap)
-        assert (fit._side_streams is not None) == overlap
+        assert (fit.sources._side_streams is not None) == overlap
         for x, _ in data:
             fit.step(x)
         outs.append({k: v.clone() for k, v in fit.finish().state_dict().items()})
@@ -525,7 +526,7 @@ def test_lookahead_steps_equal_sequential_steps(tiny_bottleneck):
         fit = PleasFitter(m1, m2, m3, t.spec, perm, costs, 0.5, len(xs) - 1, num_classes=10)
         if lookahead:
             assert list(fit.steps(xs, lookahead=True, sources_per_forward=1)) == list(range(len(xs)))
-            assert not fit._queue
+            assert not fit.sources.queue
         else:
             for x in xs:
                 fit.step(x)
@@ -574,7 +575,7 @@ def test_paired_source_forwards_equal_one_forward_per_batch(tiny_bottleneck):
                 prefetch * kw.get("sources_per_forward", 2)
         fit = PleasFitter(m1, m2, m3, t.spec, perm, costs, 0.5, len(xs) - 1, num_classes=10, sources=sources)
         assert list(fit.steps(batches, **kw)) == list(range(len(xs)))
-        assert fit.step_count == len(xs) and not fit._queue and not fit.sources._staged
+        assert fit.step_count == len(xs) and not fit.sources.queue and not fit.sources._staged
         outs.append({k: v.clone() for k, v in fit.finish().state_dict().items()})
     for other in outs[1:]:
         for k in outs[0]:
@@ -972,3 +973,58 @@ def test_normal_eq_stacked_modes_vs_oracle(tiny_basic, mode, ratio):
         assert _rel(layer.weight, want.float()) < 1e-3, (mode, n, _rel(layer.weight, want.float()))
         checked += 1
     assert checked >= (3 if ratio == 0.0 else 0), (mode, checked)      # partial merges freeze blocks of most layers
+
+
+def test_normal_eq_fitter_holds_no_adam_state_and_accumulates_what_its_kernels_give(tiny_basic):
+    """``NormalEqFitter`` shares the sources, the parameter arena and the plans with ``PleasFitter`` and allocates none of what
+    only Adam needs.  Its ``A_flat`` / ``B_flat`` after two ``step``s, for one non-stem layer on the grouped path, against the
+    same contraction without any fitter: ``hip_ops.merge_blocks`` on the very taps the two updates read, then ``NormalEqBatch``
+    and ``WgradBatch`` with that one entry.  Same kernels, another list of entries: held to 1e-5 rel-fro, the bound
+    test_hip_distributed puts on these arenas (the normal-equation tests of this file hold the solved weights to 1e-3)."""
+    from pleas.methods.partial_matching import partial_merge
+    from pleas_merging_amd import hip_ops
+    from pleas_merging_amd.methods.normal_eq import NormalEqFitter
+
+    t = tiny_basic
+    m1, m2 = _cuda_pair(t)
+    perm = t.per_key("am_perm")
+    costs = {k: v.cuda() for k, v in t.per_key("am_cost").items()}
+    m3 = partial_merge(t.spec, m1, m2, perm, costs, 0.5)
+    fit = NormalEqFitter(m1, m2, m3, t.spec, perm, costs, 0.5, 1, num_classes=10)
+    for name in ("m", "v", "g2", "_g_ext", "_g_shard", "lrs", "fwd", "loss_sum", "_replay"):
+        assert not hasattr(fit, name), name
+    kept, release = [], fit._end_update
+
+    def keep_taps():
+        kept.append(fit.gen.taps)
+        release()
+
+    fit._end_update = keep_taps
+    try:
+        for x, _ in t.batches()[:2]:
+            fit.step(x)
+    finally:
+        del fit._end_update
+    assert len(kept) == 2 and fit.gen is None
+    name = "layer4.0.conv2"
+    idx = [p.name for p in fit.plans].index(name)
+    plan, K, cout = fit.plans[idx], fit.K[idx], fit.plans[idx].w_shape[0]
+    geo = (tuple(plan.mod.kernel_size), plan.mod.stride[0], plan.mod.padding[0])
+    (in_maps, out_maps), = plan.halves
+    A, Bt = torch.zeros(K, K, device="cuda"), torch.zeros(cout, K, device="cuda")
+    neq, wgrad = hip_ops.NormalEqBatch(torch.device("cuda")), hip_ops.WgradBatch(torch.device("cuda"))
+    for taps in kept:
+        (i1, i2), (o1, o2) = taps.inputs, taps.outputs
+        ip = hip_ops.merge_blocks(i1[name], i2[name], 1, *in_maps)
+        op = hip_ops.merge_blocks(o1[name], o2[name], 1, *out_maps)
+        assert ip.shape[1] == plan.w_shape[1] >= 16 and op.shape[1] == cout       # wide enough for the grouped path
+        neq.add(ip, A, *geo)
+        wgrad.add(op, ip, Bt, *geo, flags=hip_ops.WgradBatch.ACCUMULATE | hip_ops.WgradBatch.KPOS_MAJOR)
+        neq.flush()
+        wgrad.flush()
+    oa, ob = sum(k * k for k in fit.K[:idx]), sum(k * p.w_shape[0] for k, p in zip(fit.K[:idx], fit.plans))
+    got_A, got_B = fit.A_flat[oa:oa + K * K].view(K, K), fit.B_flat[ob:ob + cout * K].view(cout, K)
+    print("A rel-fro %.2e, B rel-fro %.2e" % (_rel(got_A, A.cpu()), _rel(got_B, Bt.cpu())))
+    assert float(A.abs().sum()) > 0 and float(Bt.abs().sum()) > 0
+    assert _rel(got_A, A.cpu()) < 1e-5 and _rel(got_B, Bt.cpu()) < 1e-5
+    fit.finish()

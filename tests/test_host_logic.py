@@ -834,3 +834,65 @@ def test_config0_resnet18_weight_matching_on_the_host():
         assert torch.allclose(costs[k], want_c[k], rtol=1e-5, atol=1e-5), k
     with pytest.raises(RuntimeError):
         weight_matching(spec, models[0].state_dict(), models[1].state_dict(), max_iter=1, verbose=False)
+
+
+# ------------------------------------------------------------------ where the fitter's parts live
+def test_moved_names_keep_their_old_import_paths():
+    """The data-parallel helpers live in ``methods/data_parallel.py`` and the source side in ``methods/frozen_sources.py``;
+    every module that used to define (or hand out) one of them still does, and hands out the SAME object."""
+    from importlib import import_module      # (the packages export a FUNCTION named activation_matching)
+
+    drop_am, drop_pm = import_module("pleas.methods.activation_matching"), import_module("pleas.methods.pleas_merging")
+    am, dp, fs, ne, pm = (import_module("pleas_merging_amd.methods." + m) for m in
+                          ("activation_matching", "data_parallel", "frozen_sources", "normal_eq", "pleas_merging"))
+
+    for name in ("_dist_info", "_force_collectives", "_collectives_on", "allreduce_sum_"):
+        assert getattr(am, name) is getattr(dp, name), name
+    for name in ("dp_slice", "dp_sum_", "dp_reduce_scatter_", "dp_all_gather_", "_emulated_collective", "_SPIN"):
+        assert getattr(pm, name) is getattr(dp, name), name
+    for name in ("TapDict", "_TapView", "tap_pointers", "ActivationTap", "prepare_sources", "FrozenSources", "SourceTaps",
+                 "Generation"):
+        assert getattr(pm, name) is getattr(fs, name), name
+    # everything else the fitter module defined before the split
+    for name in ("get_gradient_mask", "_frozen_blocks", "_square_conv", "cosine_lrs", "_LayerPlan", "_identity_block",
+                 "_fallback_out_width", "MERGING_MODES", "merging_mode", "half_maps", "PleasFitter", "train"):
+        assert hasattr(pm, name), name
+    for name in ("get_gradient_mask", "train", "ActivationTap", "FrozenSources", "PleasFitter", "prepare_sources", "cosine_lrs",
+                 "dp_slice", "dp_sum_"):
+        assert getattr(drop_pm, name) is getattr(pm, name), name
+    assert drop_am.allreduce_sum_ is dp.allreduce_sum_
+    for name in ("NormalEqFitter", "exchange_solved_", "solve_owners", "_row_patterns", "_spd_solve_fp64", "train_normal_eq"):
+        assert hasattr(ne, name), name
+    assert ne.dp_sum_ is dp.dp_sum_ and ne.PleasFitter is pm.PleasFitter and ne._LayerPlan is pm._LayerPlan
+    assert issubclass(pm.PleasFitter, pm._LayerFitter) and issubclass(ne.NormalEqFitter, pm._LayerFitter)
+    assert not issubclass(ne.NormalEqFitter, pm.PleasFitter)
+
+
+def test_source_taps_unpack_as_the_four_values_of_a_launch():
+    from pleas_merging_amd.methods.frozen_sources import Generation, SourceTaps
+
+    taps = SourceTaps("x", ("in1", "out1"), ("in2", "out2"), ["ev1", "ev2"])
+    x, (in1, out1), (in2, out2), events = taps
+    assert (x, in1, out1, in2, out2, events) == ("x", "in1", "out1", "in2", "out2", ["ev1", "ev2"])
+    assert taps.inputs == ("in1", "in2") and taps.outputs == ("out1", "out2")
+    gen = Generation("batch", taps)
+    assert gen.batch == "batch" and gen.taps is taps and gen.taps.x == "x"
+
+
+def test_data_parallel_module_imports_nothing_of_the_package():
+    """``methods/data_parallel.py`` is what every other method module may import at module level, so it must import none of
+    them.  The package's ``__init__`` imports all method modules, so a fresh interpreter loads the FILE on its own: neither
+    ``activation_matching`` nor ``pleas_merging`` -- nothing of the package at all -- may come with it."""
+    import subprocess
+
+    path = os.path.join(REPO, "pleas_merging_amd", "methods", "data_parallel.py")
+    code = ("import importlib.util, sys\n"
+            "spec = importlib.util.spec_from_file_location('data_parallel_alone', %r)\n"
+            "mod = importlib.util.module_from_spec(spec)\n"
+            "spec.loader.exec_module(mod)\n"
+            "came = sorted(m for m in sys.modules if m.split('.')[0] in ('pleas', 'pleas_merging_amd'))\n"
+            "assert not came, came\n"
+            "assert mod._dist_info() == (0, 1) and not mod._collectives_on() and not mod._force_collectives()\n" % path)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("PLEAS_")}
+    out = subprocess.run([sys.executable, "-c", code], env=env, cwd=REPO, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
