@@ -383,6 +383,57 @@ int pleas_image_batch(const uint8_t* src, float* dst, const float* lut, const in
                       int64_t N, int C, int H, int W, int Ho, int Wo, int layout, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * uint8 images of MIXED sizes to normalised fp32 NCHW of one size: PIL's 8-bit bilinear resampling, flip and table lookup
+ * (csrc/image.hip; the plan and the host executor: csrc/resample_plan.hpp).
+ *
+ * Replaces: RandomResizedCrop / RandomHorizontalFlip and Resize / CenterCrop on the CPU workers of the drivers' loaders
+ *   (experiments/shared_label_space/run_domainnet.py:204-214, experiments/datasets/interface.py:14-18), in front of the
+ *   ToTensor / Normalize that pleas_image_batch's table already reproduces.  Those transforms resample PIL images, and PIL
+ *   resamples 8-bit images in integer arithmetic, so the result here has the bits of Normalize(ToTensor(PIL chain)).
+ * Layout: src one packed uint8 buffer; sample s is [H_s][W_s][C] at byte src_offset[s], any alignment, C in 1 .. 4 common to the
+ *   batch.  geom int32 [N][10] per sample: H, W, then the box y0, x0, h, w inside the image, then the virtual output size Hv, Wv
+ *   the box is resampled to, then the origin oy, ox of the Ho x Wo window of that output which is produced.
+ *     resized crop    box = the crop, (Hv, Wv) = (Ho, Wo), origin (0, 0):  img.crop((x0, y0, x0+w, y0+h)).resize((Wo, Ho), BILINEAR)
+ *     resize + window box = the whole image, origin = the window's:        img.resize((Wv, Hv), BILINEAR).crop(window)
+ *   dst fp32 [N][C][Ho][Wo] contiguous, 16-byte aligned; lut fp32 [C][256]; flip uint8 [N] or NULL = none (dst[.., x] takes the
+ *   resampled pixel Wo-1-x: RandomHorizontalFlip after the crop).
+ * Arithmetic, one pass along an axis of `in` samples to `out` (PIL's, weights in double, taps in int32):
+ *     scale = in / out;  fs = max(scale, 1);  ksize = 2 * ceil(fs) + 1;   output i:  center = (i + 0.5) * scale,
+ *     lo = max(0, (int)(center - fs + 0.5)),  hi = min(in, (int)(center + fs + 0.5)),
+ *     w_j = max(0, 1 - |(lo + j - center + 0.5) * (1 / fs)|) summed in order of j into ww, divided by ww when ww != 0,
+ *     k_j = (int)(0.5 + w_j * 2^22);   value = clamp((2^21 + sum_j k_j * in[lo + j]) >> 22, 0, 255)
+ *   horizontal pass first, stored as uint8, vertical pass second; only the source rows the window's vertical pass reads are
+ *   resampled horizontally.  The sum stays below 2^31: 2^21 + 255 * (2^22 + ksize).
+ * Determinism: integer sums, no atomics, every byte of the workspace and every element of dst written once; the plan is a pure
+ *   function of its arguments.
+ * Form: a plan built on the host (pleas_resample_plan) holds, per sample and axis, the (first tap, taps) bounds and the int32
+ *   coefficients, the sample's place in src and in the workspace, and two tables of work items (sample, first row, rows).  Two
+ *   launches for the whole batch: rows (src -> uint8 [rows_s][Wo][C] in the workspace) and planes (workspace -> flip, table in
+ *   LDS, fp32 planes in 4-byte runs side by side).  Workgroups take items with a grid stride, so samples of very different
+ *   sizes balance by their rows.  The plan is position independent: copy it to the device with the batch.
+ * Limits: a side of an image or of a virtual output is at most 16384 (a table stays below 2^31 words), N at most 2^20, the
+ *   plan below 2^31 bytes; offsets into src, the workspace and dst are 64-bit.  The kernels index with nothing that does not
+ *   come from the plan: hand pleas_image_resample the device copy of the plan whose host copy it checks.
+ * pleas_resample_plan_bytes: bytes of the plan of geom (0 and a message when geom is refused).  pleas_resample_plan: writes
+ *   it into caller memory (4-byte aligned).  pleas_resample_plan_info: info[0 .. 7] = N, C, Ho, Wo, bytes of src, bytes of the
+ *   workspace, items of the rows launch, items of the planes launch.  pleas_image_resample_host: executes a plan on the CPU, item
+ *   by item as the kernels do (an explicit host entry point like pleas_lsap_host; dst_u8, or NULL, receives the resampled
+ *   bytes [N][Ho][Wo][C] after the flip).  These four touch no device.
+ * PLEAS_EINVAL, before anything is written or enqueued: a box outside its image; a window outside its virtual output; a
+ *   non-positive size; a side above 16384; C outside 1 .. 4; a sample whose src_offset + H * W * C exceeds src_bytes or is
+ *   negative; plan memory that is NULL, unaligned or too small; a host plan without the magic word, longer than plan_bytes or
+ *   with a damaged header; a NULL src, plan, lut or dst with N > 0; a dst that is not 16-byte aligned.  A workspace below the
+ *   plan's: PLEAS_ENOMEM.  N == 0: PLEAS_OK, nothing is enqueued. */
+size_t pleas_resample_plan_bytes(const int32_t* geom, int64_t N, int Ho, int Wo);
+int pleas_resample_plan(const int32_t* geom, const int64_t* src_offset, int64_t N, int C, int Ho, int Wo, int64_t src_bytes,
+                        void* plan, size_t plan_bytes);
+int pleas_resample_plan_info(const void* plan, size_t plan_bytes, int64_t* info);
+int pleas_image_resample_host(const uint8_t* src, const void* plan, size_t plan_bytes, const float* lut, const uint8_t* flip,
+                              float* dst_f32, uint8_t* dst_u8);
+int pleas_image_resample(const uint8_t* src, const void* plan_dev, const void* plan_host, size_t plan_bytes, const float* lut,
+                         const uint8_t* flip, float* dst, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * PLeaS layer fitting: fused target/residual/loss pass and grouped weight-gradient launch.
  *
  * Replaces, for merging='perm_gradmask': the output half of get_model_orig_activations

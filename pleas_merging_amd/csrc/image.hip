@@ -20,6 +20,7 @@
 // at 0.97 to 1.01 of the byte path's time on 16 and 128 images of 224 x 224 x 3 (29 us at 128 images, the byte path then one
 // pixel at a time; with four pixels of loads in flight it takes 20 us: profiles/image_batch_bench.json).
 #include "common.hpp"
+#include "resample_plan.hpp"
 
 namespace pleas {
 
@@ -79,6 +80,115 @@ __global__ __launch_bounds__(kImgThreads) void image_batch_kernel(const uint8_t*
     }
 }
 
+// ---- pleas_image_resample: PIL's 8-bit bilinear resampling of a ragged batch in two launches (plan: resample_plan.hpp).
+//
+//   rows    ws[s][r][x][c]      = clip8(2^21 + sum_j kh[x][j] * src_s[row0 + r][lo_x + j][c])      r over the source rows the window reads
+//   planes  dst[s][c][y][x]     = lut[c][ clip8(2^21 + sum_j kv[y][j] * ws[s][lo_y + j][xs][c]) ],   xs = Wo-1-x for a flipped sample
+//
+// Replaces: RandomResizedCrop / Resize + CenterCrop on the CPU workers of the drivers' loaders
+// (experiments/shared_label_space/run_domainnet.py:204-214, experiments/datasets/interface.py:14-18), whose images come in every size.
+//
+// int32 multiply-adds only (the sum stays below 2^31: 2^21 + 255 * (2^22 + ksize)), no atomics, no floating point but the
+// table's values, every byte of ws and every element of dst written once.  A workgroup takes items (sample, first row, rows)
+// from the plan's table with a grid stride, so samples of very different sizes share the grid by their rows; inside an item
+// the 256 threads form `by` teams of `bx` lanes as in image_batch_kernel: a team takes a row, its lanes run along x side by
+// side (4-byte runs into each plane of dst).  Everything indexed with comes from the plan, which the host validated.
+constexpr int kResMaxBlocks = 8192;
+constexpr int kResStep = 4;               // outputs of a row per lane of its team (bx = the power of two at or above Wo / 4)
+
+typedef __attribute__((address_space(1))) uint8_t gu8;
+
+__device__ __forceinline__ int64_t plan64(gcint* p) { return (int64_t)(uint32_t)p[0] | ((int64_t)p[1] << 32); }
+__device__ __forceinline__ int clip8_dev(int v) { return min(max(v >> resample::kPrecisionBits, 0), 255); }
+
+template <int C>
+__global__ __launch_bounds__(kImgThreads) void resample_rows_kernel(const uint8_t* __restrict__ src_, const int32_t* __restrict__ plan_,
+                                                                    uint8_t* __restrict__ ws_, int log_bx) {
+    using namespace resample;
+    gcint* plan = PLEAS_GLOBAL_I(plan_);
+    gcu8* src = (gcu8*)src_;
+    gu8* ws = (gu8*)ws_;
+    const int bx = 1 << log_bx, by = kImgThreads >> log_bx;
+    const int tx = threadIdx.x & (bx - 1), ty = threadIdx.x >> log_bx;
+    const int Wo = plan[kHWo], items = plan[kHItemsH];
+    gcint* table = plan + plan[kHOffItemsH];
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        gcint* sm = plan + plan[kHOffSamples] + (int64_t)table[3 * it] * kSampleWords;
+        const int r0 = table[3 * it + 1], r1 = r0 + table[3 * it + 2];
+        gcu8* img = src + plan64(sm + kSSrcLo);
+        gu8* rows = ws + plan64(sm + kSWsLo);
+        gcint* hb = plan + sm[kSOffHB];
+        gcint* hk = plan + sm[kSOffHK];
+        const int ks = sm[kSKsH], W = sm[kSW], row0 = sm[kSRow0];
+        for (int r = r0 + ty; r < r1; r += by) {
+            gcu8* in = img + (int64_t)(row0 + r) * W * C;
+            gu8* out = rows + (int64_t)r * Wo * C;
+            for (int x = tx; x < Wo; x += bx) {
+                const int lo = hb[2 * x], n = hb[2 * x + 1];
+                gcint* k = hk + (int64_t)x * ks;
+                gcu8* p = in + (int64_t)lo * C;
+                int acc[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] = 1 << (kPrecisionBits - 1);
+                for (int j = 0; j < n; ++j) {
+                    const int kj = k[j];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) acc[c] += kj * (int)p[j * C + c];
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c) out[x * C + c] = (uint8_t)clip8_dev(acc[c]);
+            }
+        }
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(kImgThreads) void resample_planes_kernel(const uint8_t* __restrict__ ws_, const int32_t* __restrict__ plan_,
+                                                                      const float* __restrict__ lut, const uint8_t* __restrict__ flip,
+                                                                      float* __restrict__ dst_, int log_bx) {
+    using namespace resample;
+    __shared__ float lds_table[C * 256];
+    for (int i = threadIdx.x; i < C * 256; i += kImgThreads) lds_table[i] = lut[i];
+    __syncthreads();
+
+    gcint* plan = PLEAS_GLOBAL_I(plan_);
+    gcu8* ws = (gcu8*)ws_;
+    gfloat* dst = PLEAS_GLOBAL_W(dst_);
+    const int bx = 1 << log_bx, by = kImgThreads >> log_bx;
+    const int tx = threadIdx.x & (bx - 1), ty = threadIdx.x >> log_bx;
+    const int Ho = plan[kHHo], Wo = plan[kHWo], items = plan[kHItemsV];
+    const uint64_t plane = (uint64_t)Ho * (uint64_t)Wo;
+    gcint* table = plan + plan[kHOffItemsV];
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        const int s = table[3 * it];
+        gcint* sm = plan + plan[kHOffSamples] + (int64_t)s * kSampleWords;
+        const int y0 = table[3 * it + 1], y1 = y0 + table[3 * it + 2];
+        gcu8* rows = ws + plan64(sm + kSWsLo);
+        gcint* vb = plan + sm[kSOffVB];
+        gcint* vk = plan + sm[kSOffVK];
+        const int ks = sm[kSKsV];
+        const bool fl = flip && flip[s];
+        for (int y = y0 + ty; y < y1; y += by) {
+            const int lo = vb[2 * y], n = vb[2 * y + 1];
+            gcint* k = vk + (int64_t)y * ks;
+            gfloat* d = dst + (((uint64_t)s * C) * (uint64_t)Ho + (uint64_t)y) * (uint64_t)Wo;      // plane 0 of the row
+            for (int x = tx; x < Wo; x += bx) {
+                gcu8* p = rows + ((int64_t)lo * Wo + (fl ? Wo - 1 - x : x)) * C;
+                int acc[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] = 1 << (kPrecisionBits - 1);
+                for (int j = 0; j < n; ++j) {
+                    const int kj = k[j];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) acc[c] += kj * (int)p[(int64_t)j * Wo * C + c];
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c) d[(uint64_t)c * plane + x] = lds_table[c * 256 + clip8_dev(acc[c])];
+            }
+        }
+    }
+}
+
 }  // namespace pleas
 
 using namespace pleas;
@@ -114,5 +224,74 @@ extern "C" int pleas_image_batch(const uint8_t* src, float* dst, const float* lu
     }
 #undef PLEAS_IMAGE_LAUNCH
     PLEAS_LAUNCH_CHECK("image_batch_kernel");
+    return PLEAS_OK;
+}
+
+extern "C" size_t pleas_resample_plan_bytes(const int32_t* geom, int64_t N, int Ho, int Wo) {
+    resample::Layout L;
+    if (const char* e = resample::layout_of(geom, N, Ho, Wo, L)) {
+        bad_arg(e);
+        return 0;
+    }
+    return (size_t)L.words * 4;
+}
+
+extern "C" int pleas_resample_plan(const int32_t* geom, const int64_t* src_offset, int64_t N, int C, int Ho, int Wo, int64_t src_bytes,
+                                   void* plan, size_t plan_bytes) {
+    if (const char* e = resample::build_plan(geom, src_offset, N, C, Ho, Wo, src_bytes, (int32_t*)plan, plan_bytes)) return bad_arg(e);
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_resample_plan_info(const void* plan_, size_t plan_bytes, int64_t* info) {
+    const int32_t* plan = (const int32_t*)plan_;
+    if (const char* e = resample::check_header(plan, plan_bytes)) return bad_arg(e);
+    if (!info) return bad_arg("image_resample: null info");
+    using namespace resample;
+    info[0] = plan[kHN], info[1] = plan[kHC], info[2] = plan[kHHo], info[3] = plan[kHWo];
+    info[4] = pair64(plan + kHSrcLo), info[5] = pair64(plan + kHWsLo), info[6] = plan[kHItemsH], info[7] = plan[kHItemsV];
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_image_resample_host(const uint8_t* src, const void* plan_, size_t plan_bytes, const float* lut, const uint8_t* flip,
+                                         float* dst_f32, uint8_t* dst_u8) {
+    const int32_t* plan = (const int32_t*)plan_;
+    if (const char* e = resample::check_header(plan, plan_bytes)) return bad_arg(e);
+    if (plan[resample::kHN] == 0) return PLEAS_OK;
+    if (!src || !lut || !dst_f32) return bad_arg("image_resample_host: null src, lut or dst");
+    std::vector<uint8_t> ws((size_t)resample::pair64(plan + resample::kHWsLo));
+    resample::execute(src, plan, lut, flip, dst_f32, dst_u8, ws.data());
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_image_resample(const uint8_t* src, const void* plan_dev, const void* plan_host, size_t plan_bytes, const float* lut,
+                                    const uint8_t* flip, float* dst, void* ws, size_t ws_bytes, void* stream_) {
+    using namespace resample;
+    const int32_t* plan = (const int32_t*)plan_host;
+    if (const char* e = check_header(plan, plan_bytes)) return bad_arg(e);
+    if (plan[kHN] == 0) return PLEAS_OK;      // nothing to write
+    if (!src || !plan_dev || !lut || !dst) return bad_arg("image_resample: null src, plan, lut or dst");
+    if (((uintptr_t)plan_dev & 3)) return bad_arg("image_resample: the device plan must be 4-byte aligned");
+    if ((uintptr_t)dst & 15) return bad_arg("image_resample: dst must be 16-byte aligned");
+    const size_t need = (size_t)pair64(plan + kHWsLo);
+    if (!ws || ws_bytes < need) return workspace_too_small("image_resample", need);
+    const int C = plan[kHC], Wo = plan[kHWo];
+    const int lanes = (int)ceil_div(Wo, kResStep);
+    int log_bx = 0;
+    while ((1 << log_bx) < lanes && (1 << log_bx) < kImgThreads) ++log_bx;
+    const dim3 grid_h((unsigned)std::min(plan[kHItemsH], kResMaxBlocks)), grid_v((unsigned)std::min(plan[kHItemsV], kResMaxBlocks));
+    hipStream_t stream = (hipStream_t)stream_;
+#define PLEAS_RESAMPLE_LAUNCH(CH)                                                                                                    \
+    hipLaunchKernelGGL(resample_rows_kernel<CH>, grid_h, dim3(kImgThreads), 0, stream, src, (const int32_t*)plan_dev, (uint8_t*)ws,   \
+                       log_bx);                                                                                                      \
+    hipLaunchKernelGGL(resample_planes_kernel<CH>, grid_v, dim3(kImgThreads), 0, stream, (const uint8_t*)ws,                         \
+                       (const int32_t*)plan_dev, lut, flip, dst, log_bx)
+    switch (C) {
+        case 1: PLEAS_RESAMPLE_LAUNCH(1); break;
+        case 2: PLEAS_RESAMPLE_LAUNCH(2); break;
+        case 3: PLEAS_RESAMPLE_LAUNCH(3); break;
+        default: PLEAS_RESAMPLE_LAUNCH(4); break;
+    }
+#undef PLEAS_RESAMPLE_LAUNCH
+    PLEAS_LAUNCH_CHECK("resample kernels");
     return PLEAS_OK;
 }

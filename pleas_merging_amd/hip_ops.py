@@ -2,7 +2,7 @@
 
 PyTorch is used for device memory and streams only: every function here enqueues a
 hand-written gfx950 kernel on torch's current stream via ctypes.  Inputs must be fp32
-CUDA(=HIP) tensors (``image_batch``: uint8 images); anything else raises -- there is no
+CUDA(=HIP) tensors (``image_batch`` / ``image_resample``: uint8 images); anything else raises -- there is no
 eager/CPU fallback.
 """
 from __future__ import annotations
@@ -1014,6 +1014,152 @@ def image_batch(src_u8: torch.Tensor, table: torch.Tensor, out: Optional[torch.T
                                        origin_d.data_ptr() if origin_d is not None else None,
                                        flip_d.data_ptr() if flip_d is not None else None, N, C, H, W, Ho, Wo,
                                        IMAGE_LAYOUTS[layout], _stream()), "pleas_image_batch")
+    return out
+
+
+RESAMPLE_GEOM = 10      # int32 per sample: H, W, y0, x0, h, w, Hv, Wv, oy, ox (include/pleas_hip.h)
+
+
+def _resample_geom(geom) -> torch.Tensor:
+    if torch.is_tensor(geom) and geom.is_cuda:
+        raise PleasHipError("image_resample_plan: the geometry is checked on the host: pass a CPU tensor or a sequence")
+    geom = torch.as_tensor(geom)
+    if geom.dtype.is_floating_point or geom.dtype == torch.bool or geom.dim() != 2 or geom.shape[1] != RESAMPLE_GEOM:
+        raise PleasHipError("image_resample_plan: geom must hold integers of shape (N, %d), got %s %s"
+                            % (RESAMPLE_GEOM, geom.dtype, tuple(geom.shape)))
+    if geom.numel() and (int(geom.min()) < -(1 << 31) or int(geom.max()) >= 1 << 31):
+        raise PleasHipError("image_resample_plan: geom does not fit int32")
+    return geom.to(torch.int32).contiguous()
+
+
+def image_resample_plan_bytes(geom, size: Tuple[int, int]) -> int:
+    """Bytes of the plan of ``geom`` for outputs of ``size=(Ho, Wo)`` (``pleas_resample_plan_bytes``; refusals raise)."""
+    geom = _resample_geom(geom)
+    n = _lib.lib().pleas_resample_plan_bytes(geom.data_ptr(), geom.shape[0], int(size[0]), int(size[1]))
+    if n == 0:
+        raise PleasHipError("pleas_resample_plan_bytes: %s" % _lib.lib().pleas_last_error().decode())
+    return n
+
+
+def image_resample_plan(geom, src_offset, channels: int, size: Tuple[int, int], src_bytes: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The plan of ``image_resample`` for one ragged batch (``pleas_resample_plan``; host only): a uint8 tensor, pinned where a
+    GPU is present, or the leading bytes of ``out`` (a contiguous uint8 HOST tensor on a 4-byte boundary, e.g. a staging buffer
+    that also takes the images, so that one copy carries both).
+
+    ``geom``: HOST integers [N, 10] per sample -- ``H, W`` (image), ``y0, x0, h, w`` (box), ``Hv, Wv`` (virtual output the box
+    is resampled to), ``oy, ox`` (origin of the ``size=(Ho, Wo)`` window produced).  ``src_offset``: HOST integers [N], the byte
+    offset of each packed uint8 ``[H, W, C]`` image in a buffer of ``src_bytes``.  Everything is validated by the library; a
+    refusal raises ``PleasHipError``."""
+    geom = _resample_geom(geom)
+    n = geom.shape[0]
+    if torch.is_tensor(src_offset) and src_offset.is_cuda:
+        raise PleasHipError("image_resample_plan: offsets are checked on the host: pass a CPU tensor or a sequence")
+    src_offset = torch.as_tensor(src_offset, dtype=torch.int64) if not torch.is_tensor(src_offset) and not len(src_offset) \
+        else torch.as_tensor(src_offset)
+    if src_offset.dtype.is_floating_point or src_offset.dtype == torch.bool or tuple(src_offset.shape) != (n,):
+        raise PleasHipError("image_resample_plan: src_offset must hold %d integers, got %s %s" % (n, src_offset.dtype, tuple(src_offset.shape)))
+    src_offset = src_offset.to(torch.int64).contiguous()
+    nbytes = image_resample_plan_bytes(geom, size)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8)
+        if torch.cuda.is_available():
+            out = out.pin_memory()
+    elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.is_cuda or not out.is_contiguous() or out.numel() < nbytes
+          or out.data_ptr() % 4):
+        raise PleasHipError("image_resample_plan: out must be a contiguous uint8 host tensor of at least %d bytes on a 4-byte boundary" % nbytes)
+    plan = out.view(-1)[:nbytes]
+    check(_lib.lib().pleas_resample_plan(geom.data_ptr(), src_offset.data_ptr(), n, int(channels), int(size[0]), int(size[1]),
+                                         int(src_bytes), plan.data_ptr(), nbytes), "pleas_resample_plan")
+    return plan
+
+
+def image_resample_plan_info(plan: torch.Tensor) -> dict:
+    """What a HOST plan says of itself: ``n, channels, size, src_bytes, ws_bytes, items`` (``pleas_resample_plan_info``)."""
+    if not torch.is_tensor(plan) or plan.dtype != torch.uint8 or plan.is_cuda or not plan.is_contiguous():
+        raise PleasHipError("image_resample: the host plan must be a contiguous uint8 CPU tensor (image_resample_plan's)")
+    info = (ctypes.c_int64 * 8)()
+    check(_lib.lib().pleas_resample_plan_info(plan.data_ptr(), plan.numel(), info), "pleas_resample_plan_info")
+    return {"n": info[0], "channels": info[1], "size": (info[2], info[3]), "src_bytes": info[4], "ws_bytes": info[5],
+            "items": (info[6], info[7])}
+
+
+def _resample_flip(flip, n: int):
+    if flip is None:
+        return None
+    flip = torch.as_tensor(flip)
+    if tuple(flip.shape) != (n,):
+        raise PleasHipError("image_resample: flip must hold %d flags, got shape %s" % (n, tuple(flip.shape)))
+    return flip if flip.dtype == torch.uint8 and flip.is_contiguous() else flip.ne(0).to(torch.uint8).contiguous()
+
+
+def image_resample_host(src_u8: torch.Tensor, plan: torch.Tensor, table: torch.Tensor, flip=None):
+    """A plan executed on the CPU, item by item as the two kernels do (``pleas_image_resample_host``): returns ``(fp32 [N, C, Ho,
+    Wo], uint8 [N, Ho, Wo, C])`` -- the resampled bytes through ``table``, and the bytes themselves, both after the flip.  The
+    explicit host entry point of this path (what the GPU tests compare with); nothing here touches a device."""
+    info = image_resample_plan_info(plan)
+    n, c, (ho, wo) = info["n"], info["channels"], info["size"]
+    if not torch.is_tensor(src_u8) or src_u8.dtype != torch.uint8 or src_u8.is_cuda or not src_u8.is_contiguous():
+        raise PleasHipError("image_resample_host: src must be a contiguous uint8 CPU tensor")
+    if src_u8.numel() < info["src_bytes"]:
+        raise PleasHipError("image_resample_host: src holds %d bytes, the plan was built for %d" % (src_u8.numel(), info["src_bytes"]))
+    if table.is_cuda or table.dtype != torch.float32 or tuple(table.shape) != (c, 256) or not table.is_contiguous():
+        raise PleasHipError("image_resample_host: table must be a contiguous fp32 [%d, 256] CPU tensor" % c)
+    flip = _resample_flip(flip, n)
+    if flip is not None and flip.is_cuda:
+        raise PleasHipError("image_resample_host: flip flags must be host values")
+    f32, u8 = torch.empty((n, c, ho, wo), dtype=torch.float32), torch.empty((n, ho, wo, c), dtype=torch.uint8)
+    check(_lib.lib().pleas_image_resample_host(src_u8.data_ptr(), plan.data_ptr(), plan.numel(), table.data_ptr(),
+                                               flip.data_ptr() if flip is not None else None, f32.data_ptr(), u8.data_ptr()),
+          "pleas_image_resample_host")
+    return f32, u8
+
+
+def image_resample(src_u8: torch.Tensor, plan_dev: torch.Tensor, plan: torch.Tensor, table: torch.Tensor, flip=None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Packed uint8 images of mixed sizes on the GPU to normalised fp32 [N, C, Ho, Wo]: PIL's 8-bit bilinear resampling (crop +
+    resize, or resize + window), flip and table lookup in two launches (``pleas_image_resample``).
+
+    ``src_u8``: the packed buffer the plan was built for, contiguous uint8 on the GPU, any alignment.  ``plan``: the HOST plan
+    of ``image_resample_plan``; ``plan_dev``: its copy on src's device (uint8, 4-byte aligned) -- the kernels index with
+    nothing else.  ``table``: ``image_table(...)`` on the device.  ``flip``: [N] flags, host values (uploaded) or a uint8 tensor
+    already on the device.  ``out``: a contiguous, 16-byte aligned fp32 [N, C, Ho, Wo] tensor on the device (allocated when
+    not given).  The scratch for the horizontally resampled rows comes from the stream's ``Workspace``."""
+    if not torch.is_tensor(src_u8) or src_u8.dtype != torch.uint8:
+        raise PleasHipError("image_resample: src must be a uint8 tensor (got %s)" % getattr(src_u8, "dtype", type(src_u8)))
+    if not src_u8.is_contiguous():
+        raise PleasHipError("image_resample: src must be contiguous (one packed buffer)")
+    info = image_resample_plan_info(plan)
+    n, c, (ho, wo) = info["n"], info["channels"], info["size"]
+    if src_u8.numel() < info["src_bytes"]:
+        raise PleasHipError("image_resample: src holds %d bytes, the plan was built for %d" % (src_u8.numel(), info["src_bytes"]))
+    flip = _resample_flip(flip, n)
+    if out is not None and (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (n, c, ho, wo) or not out.is_contiguous()
+                            or out.data_ptr() % 16):
+        raise PleasHipError("image_resample: out must be a contiguous, 16-byte aligned fp32 tensor of shape %s on the GPU"
+                            % ((n, c, ho, wo),))
+    if not src_u8.is_cuda:
+        raise PleasHipError("HIP path needs tensors on the GPU (got device %s); no CPU fallback" % src_u8.device)
+    dev = src_u8.device
+    _need_gpu(table)
+    if table.device != dev or tuple(table.shape) != (c, 256) or not table.is_contiguous():
+        raise PleasHipError("image_resample: table must be a contiguous fp32 [%d, 256] tensor on src's device" % c)
+    if (not torch.is_tensor(plan_dev) or plan_dev.dtype != torch.uint8 or plan_dev.device != dev or not plan_dev.is_contiguous()
+            or plan_dev.numel() < plan.numel() or plan_dev.data_ptr() % 4):
+        raise PleasHipError("image_resample: plan_dev must be the plan's %d bytes as a contiguous uint8 tensor on src's device, "
+                            "4-byte aligned" % plan.numel())
+    if out is None:
+        out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=dev)
+    elif out.device != dev:
+        raise PleasHipError("image_resample: out must be on src's device")
+    if n == 0:
+        return out
+    if flip is not None and flip.device != dev:
+        flip = flip.to(dev)
+    ws = Workspace.get(dev).reserve(info["ws_bytes"])
+    check(_lib.lib().pleas_image_resample(src_u8.data_ptr(), plan_dev.data_ptr(), plan.data_ptr(), plan.numel(), table.data_ptr(),
+                                          flip.data_ptr() if flip is not None else None, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _stream()), "pleas_image_resample")
     return out
 
 

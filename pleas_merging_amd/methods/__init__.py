@@ -15,4 +15,4 @@ from .evaluation import (get_fc_perm, permute_final_features, final_feature_map,
                          train_eval_linear_probe)
 from .linear_probe import HipProbeHead, cosine_lrs_eta_min
 from .source_forward import InferenceBackbone
-from .images import DeviceImages
+from .images import DeviceImages, ragged_collate
