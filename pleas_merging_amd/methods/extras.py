@@ -25,6 +25,7 @@ from torch import nn
 
 from ..core.utils import Axis, Permutation, PermutationSpec
 from .data_parallel import _dist_info
+from .source_forward import batch_runs, fuse_bn_act
 
 
 BN_RESET_BACKBONES = ("modules", "hip")
@@ -38,8 +39,6 @@ def _bn_reset_runner(model: nn.Module, fused: bool, backbone: str = "modules"):
     as well (``fuse_bn_act(train_convs=True)``): a convolution followed by a train-mode BatchNorm leaves that BatchNorm's batch
     statistics from its epilogue (``HipConvBnStats``) -- no vendor convolution, so the pass is bit-for-bit repeatable."""
     if fused and next(iter(model.parameters())).is_cuda:
-        from .source_forward import fuse_bn_act
-
         return fuse_bn_act(model, train_stats=True, train_convs=backbone == "hip") or model
     return model
 
@@ -79,38 +78,17 @@ def reset_bn_stats(model: nn.Module, dataloader: Iterable, num_batches: int = 10
         m.reset_running_stats()
     runner = _bn_reset_runner(model, fused, backbone)        # built AFTER model.train(): the rewrite folds what is in train mode
     if world == 1:
-        # HIP path: consecutive batches of equal shape share a forward (the vendor convolutions run faster per sample on
-        # 64 samples than on 16) -- every BatchNorm still folds each batch on its own samples, in order, in one launch, so
-        # statistics, running statistics and counters are those of one forward per batch.  Default: forwards of up to 64
-        # samples, at most 4 batches.
-        together = getattr(runner, "all_batch_statistics_folded", False) and hasattr(runner, "batches_per_forward")
-        per, run = (None if batches_per_forward is None else max(1, int(batches_per_forward))), []
-
-        def forward(xs):
+        # HIP path: consecutive batches of equal shape share a forward (``source_forward.batch_runs``; the vendor convolutions
+        # run faster per sample on 64 samples than on 16) -- every BatchNorm still folds each batch on its own samples, in
+        # order, in one launch, so statistics, running statistics and counters are those of one forward per batch.
+        state = getattr(runner, "batches_per_forward", None) if getattr(runner, "all_batch_statistics_folded", False) else None
+        batches = (batch[0].to(device).float() for batch, _ in zip(dataloader, range(num_batches)))
+        for xs in batch_runs(batches, batches_per_forward, single=state is None):
             if len(xs) == 1:
                 runner(xs[0])
-                return
-            runner.batches_per_forward.parts = len(xs)
-            try:
-                runner(torch.cat(xs, 0))
-            finally:
-                runner.batches_per_forward.parts = 1
-
-        for i, batch in enumerate(dataloader):
-            if i >= num_batches:
-                break
-            x = batch[0].to(device).float()
-            if not together:
-                runner(x)
-                continue
-            if per is None:
-                per = max(1, min(4, 64 // max(1, int(x.shape[0]))))
-            if run and (x.shape != run[0].shape or len(run) == per):
-                forward(run)
-                run = []
-            run.append(x)
-        if run:
-            forward(run)
+            else:
+                with state.of(len(xs)):
+                    runner(torch.cat(xs, 0))
         return model
 
     import torch.distributed as dist

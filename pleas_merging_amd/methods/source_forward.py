@@ -27,6 +27,7 @@ Values differ from the vendor BN kernel by fp32 rounding only (one fma instead o
 """
 from __future__ import annotations
 
+import contextlib
 import operator
 import os
 from typing import Callable, Optional
@@ -270,8 +271,34 @@ def _bn_act_pool(x, scale, shift, kernel, stride, padding, relu):
 
 class BatchesPerForward:
     """How many batches lie back to back in the tensor a rewritten graph is forwarding right now (read by its train-mode
-    BatchNorm folds); the caller sets ``parts`` around the call."""
+    BatchNorm folds); the caller sets ``parts`` around the call: ``with state.of(k): graph(torch.cat(k batches))``."""
     parts = 1
+
+    @contextlib.contextmanager
+    def of(self, parts: int):
+        self.parts = parts
+        try:
+            yield self
+        finally:
+            self.parts = 1
+
+
+def batch_runs(batches, per_forward: Optional[int] = None, single: bool = False):
+    """Which batches share a forward: lists of consecutive ``batches`` of equal shape, at most ``per_forward`` long
+    (``single``: one).  Default: forwards of up to 64 samples, at most 4 batches -- ``max(1, min(4, 64 // N))``, fixed when
+    the first batch shows its size N.  A run is yielded only once the batch after it has been pulled (or the input has
+    ended): an iterable that enqueues each batch's host-to-device copy does so beside the previous run's forward."""
+    limit = 1 if single else None if per_forward is None else max(1, int(per_forward))
+    run = []
+    for x in batches:
+        if limit is None:
+            limit = max(1, min(4, 64 // max(1, int(x.shape[0]))))
+        if run and (x.shape != run[0].shape or len(run) == limit):
+            yield run
+            run = []
+        run.append(x)
+    if run:
+        yield run
 
 
 def _pair(v):
@@ -523,7 +550,7 @@ def _graph_module(model: nn.Module, graph: torch.fx.Graph, mods, constants: dict
             root[node.target] = obj
     gm = torch.fx.GraphModule(root, graph, class_name=type(model).__name__)
     gm.train(model.training)
-    gm.batches_per_forward = state      # reset_bn_stats: `gm.batches_per_forward.parts = k` around a k-batch forward
+    gm.batches_per_forward = state      # reset_bn_stats: `with gm.batches_per_forward.of(k):` around a k-batch forward
     # does every normalisation layer with batch statistics go through a per-batch fold?  (only then may batches share a forward)
     gm.all_batch_statistics_folded = not uses_batch_statistics(gm)
     return gm

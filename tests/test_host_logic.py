@@ -496,6 +496,10 @@ def test_split_twin_graph_defers_sinks_and_keeps_inplace_targets(tiny_bottleneck
     interleaved one -- also for a model that overwrites tracked tensors in place (``out += identity``, ``relu_``)."""
     import importlib
 
+    if GOLDEN not in sys.path:
+        sys.path.insert(0, GOLDEN)
+    from make_golden_graphs import InPlace      # the model's home: the recipe of the graph pins, which records its twins
+
     am = importlib.import_module("pleas_merging_amd.methods.activation_matching")
 
     class Streams:   # stand-in for _SideStream on a machine without a GPU
@@ -526,18 +530,6 @@ def test_split_twin_graph_defers_sinks_and_keeps_inplace_targets(tiny_bottleneck
 
         return emit
 
-    class InPlace(torch.nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.c1, self.c2 = torch.nn.Conv2d(3, 4, 3, padding=1), torch.nn.Conv2d(4, 4, 3, padding=1)
-            self.act = torch.nn.ReLU(inplace=True)
-
-        def forward(self, x):
-            a = self.act(self.c1(x))
-            b = self.c2(a)
-            b += a
-            return b.relu_()
-
     t = tiny_bottleneck
     cases = [(t.m1, t.m2, [nax for g in t.spec.values() for nax in g.node], t.batches()[0][0])]
     torch.manual_seed(0)
@@ -566,6 +558,79 @@ def test_split_twin_graph_defers_sinks_and_keeps_inplace_targets(tiny_bottleneck
     with pytest.raises(ValueError):
         am._build_twin(m1, m2, axes, emitter({}), keep_inputs=False, side_stream=Streams())
 
+
+
+@pytest.mark.parametrize("sizes, kwargs, want", [
+    ([16] * 5 + [8] + [16], {}, [4, 1, 1, 1]),
+    ([8] + [16] * 5, {}, [1, 4, 1]),            # the limit is fixed by the first batch: min(4, 64 // 8) = 4
+    ([64] * 3, {}, [1, 1, 1]),
+    ([100] * 2, {}, [1, 1]),
+    ([3] * 9, {}, [4, 4, 1]),
+    ([16] * 5, {"per_forward": 2}, [2, 2, 1]),
+    ([16] * 5, {"single": True}, [1] * 5),
+    ([], {}, []),
+])
+def test_batch_runs_groups_consecutive_equal_batches(sizes, kwargs, want):
+    """``source_forward.batch_runs``: which batches share a forward, in the matching and in the BatchNorm reset alike."""
+    from pleas_merging_amd.methods.source_forward import batch_runs
+
+    batches = [torch.full((n, 3, 4, 4), float(i)) for i, n in enumerate(sizes)]
+    runs = list(batch_runs(iter(batches), **kwargs))
+    assert [len(r) for r in runs] == want
+    assert all(a is b for a, b in zip([x for r in runs for x in r], batches)) and sum(want) == len(batches)
+    assert all(x.shape == r[0].shape for r in runs for x in r)
+
+
+def test_batch_runs_pulls_the_next_batch_before_it_yields_a_run():
+    """The pull is where the matching enqueues the next host-to-device copy: it must precede the previous run's forward."""
+    from pleas_merging_amd.methods.source_forward import batch_runs
+
+    pulled = []
+
+    def source():
+        for i in range(7):
+            pulled.append(i)
+            yield torch.zeros(16, 3, 4, 4)
+
+    runs = batch_runs(source(), None)
+    first = next(runs)
+    assert len(first) == 4 and pulled == [0, 1, 2, 3, 4]      # one more than the run holds
+    assert len(next(runs)) == 3 and pulled == list(range(7))   # the input ended: nothing further to pull
+    assert next(runs, None) is None
+
+
+def test_batches_per_forward_state_is_scoped_and_shared(monkeypatch):
+    """``BatchesPerForward.of(k)``: ``parts`` is k inside, 1 after a normal exit and after an exception; one state handed to
+    two train-mode BatchNorm folds is the one both read."""
+    from pleas_merging_amd.methods import source_forward as sf
+
+    state = sf.BatchesPerForward()
+    assert state.parts == 1
+    with state.of(3) as inside:
+        assert inside is state and state.parts == 3
+    assert state.parts == 1
+    with pytest.raises(KeyError):
+        with state.of(4):
+            assert state.parts == 4
+            raise KeyError("forward failed")
+    assert state.parts == 1
+    seen = []
+
+    class Recorder:      # in place of the kernel wrapper: what the fold hands it is the state's count at call time
+        def __init__(self, bn):
+            pass
+
+        def __call__(self, x, parts):
+            seen.append(parts)
+
+    monkeypatch.setattr(sf.hip_ops, "BnTrainFold", Recorder)
+    folds = [sf._train_fold(torch.nn.BatchNorm2d(4), "bn%d" % i, state) for i in (0, 1)]
+    assert all(f.train_fold_of[2] is state for f in folds)
+    with state.of(2):
+        for f in folds:
+            f(None)
+    folds[0](None)
+    assert seen == [2, 2, 1]
 
 
 @pytest.mark.parametrize("fname", ["tiny_basic.npz", "tiny_bottleneck.npz"])
