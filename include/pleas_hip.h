@@ -56,6 +56,10 @@ const char* pleas_last_error(void);
 size_t pleas_gram_ws_bytes(int B, int C, int64_t HW);
 int pleas_gram_accum(const float* x, const float* y, int B, int C, int64_t HW, int epilogue, int accumulate,
                      float* acc, void* ws, size_t ws_bytes, void* stream);
+/* Host only (no GPU): the plan pleas_gram_accum makes for a shape, given whether both operands are 16-byte aligned:
+ * info[0] tile (64 / 128), [1] floats per load (4 / 1), [2] S, the split-K slabs, [3] chunks of 32 k per slab.  Shapes the
+ * launch refuses are refused with the same message. */
+int pleas_gram_plan_info(int B, int C, int64_t HW, int aligned, int* info);
 
 /* Grouped form: ALL tracked nodes of one batch in one contraction grid plus one reduce grid.
  *
@@ -91,6 +95,13 @@ typedef struct pleas_gram_node {
     const float* shift_y;
 } pleas_gram_node;
 size_t pleas_gram_batch_ws_bytes(const pleas_gram_node* nodes, int n_nodes, const int* group_C, int n_groups);
+/* Host only (no GPU, pointers may be NULL except a derived node's scale / shift): what the plan builder of pleas_gram_batch
+ * decides, six ints per node: [0] the tile form `variant` (0: 128-row tiles, 16-byte loads; 1: 128, 4-byte loads; 2 / 3: the
+ * same with 64 rows; 4 / 5: 128 / 64 rows on the K axis padded to four pixels per group, HW % 4 != 0 and HW >= 4), [1] S, the
+ * slabs of the K axis (0 for a derived node), [2] chunks of 32 k per slab, [3] tiles per side, [4] HWp, the pixels per sample
+ * on the K axis (HW outside the padded forms), [5] 1 when the node also writes row sums (a derived node's source).  A list
+ * the launch refuses is refused with the same message.  Returns 0 or a negative error code. */
+int pleas_gram_batch_plan_info(const pleas_gram_node* nodes, int n_nodes, const int* group_C, int n_groups, int* info);
 int pleas_gram_batch(const pleas_gram_node* nodes, int n_nodes, float* const* group_acc, const int* group_C,
                      int n_groups, int epilogue, int accumulate, void* ws, size_t ws_bytes, int ws_fresh, void* stream);
 
@@ -602,6 +613,12 @@ int pleas_normal_eq_accum(const pleas_neq_layer* layers, int n_layers, void* ws,
  * info[1] = flops the grid executes, info[2] = work items, info[3] = blocks left to finalize. */
 int pleas_normal_eq_finalize(const pleas_neq_layer* layers, int n_layers, void* stream);
 int pleas_normal_eq_plan_info(const pleas_neq_layer* layers, int n_layers, double* info);
+/* Host only (no GPU, pointers may be NULL): per layer what the plan builder of pleas_normal_eq_accum decides, five ints:
+ * [0] the tile form `variant` (bit 0: 64-wide tiles, bit 1: 4-byte loads, bits 2-3: 0 direct (1x1, stride 1, no padding),
+ * 1 shifted loader, 2 lag classes -- the values 0-3, 6-7, 8-11), [1] S, the slabs of the pixel axis, [2] tiles per side of a
+ * block, [3] block tiles contracted, [4] blocks left to pleas_normal_eq_finalize.  A geometry the launch refuses is refused
+ * with the same message. */
+int pleas_normal_eq_layer_info(const pleas_neq_layer* layers, int n_layers, int* info);
 
 /* Batched SPD solve of the normal equations (blocked Cholesky + forward/back substitution, panel 64,
  * trailing updates on fp32 MFMA tiles).  For every problem p:  X (A_p + lambda*mean(diag A_p) I) = Bt_p,

@@ -100,6 +100,9 @@ SIGNATURES = {
     "pleas_wgrad_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "pleas_wgrad_plan_info": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "pleas_gram_batch_ws_bytes": (c_size_t, [c_void_p, c_int, POINTER(c_int), c_int]),
+    "pleas_gram_plan_info": (c_int, [c_int, c_int, c_int64, c_int, POINTER(c_int)]),
+    "pleas_gram_batch_plan_info": (c_int, [c_void_p, c_int, POINTER(c_int), c_int, POINTER(c_int)]),
+    "pleas_normal_eq_layer_info": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "pleas_gram_batch": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int), c_int, c_int, c_int, c_void_p,
                                  c_size_t, c_int, c_void_p]),
 }

@@ -509,12 +509,29 @@ extern "C" size_t pleas_gram_ws_bytes(int B, int C, int64_t HW) {
     return make_plan(B, C, HW, true).ws_bytes;  // alignment does not change the size
 }
 
-extern "C" int pleas_gram_accum(const float* x, const float* y, int B, int C, int64_t HW, int epilogue, int accumulate,
-                                float* acc, void* ws, size_t ws_bytes, void* stream_) {
-    if (!x || !y || !acc) return bad_arg("null tensor pointer");
+// the shapes the single-node launch takes (the launch and its host query refuse the others alike)
+static int gram_shape_check(int B, int C, int64_t HW) {
     if (B <= 0 || C <= 0 || HW <= 0) return bad_arg("B, C, HW must be positive");
     if ((int64_t)B * HW >= (1ll << 31) || HW >= (1ll << 31)) return bad_arg("B*HW must be < 2^31");
     if ((int64_t)B * C * HW >= (1ll << 30)) return bad_arg("B*C*HW must be < 2^30 (the tile addresses an operand with 32-bit byte offsets)");
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_gram_plan_info(int B, int C, int64_t HW, int aligned, int* info) {
+    if (!info) return bad_arg("gram_plan_info: null output");
+    if (const int rc = gram_shape_check(B, C, HW); rc != PLEAS_OK) return rc;
+    const GramPlan p = make_plan(B, C, HW, aligned != 0);
+    info[0] = p.tile;
+    info[1] = p.vec;
+    info[2] = p.S;
+    info[3] = p.cps;
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_gram_accum(const float* x, const float* y, int B, int C, int64_t HW, int epilogue, int accumulate,
+                                float* acc, void* ws, size_t ws_bytes, void* stream_) {
+    if (!x || !y || !acc) return bad_arg("null tensor pointer");
+    if (const int rc = gram_shape_check(B, C, HW); rc != PLEAS_OK) return rc;
     if (epilogue != PLEAS_EPI_INNER && epilogue != PLEAS_EPI_NEG_CDIST) return bad_arg("epilogue");
     const bool aligned = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
     const GramPlan p = make_plan(B, C, HW, aligned);
@@ -584,6 +601,7 @@ struct BatchPlan {
     std::vector<GramItemDev> items;
     std::vector<GramGroupDev> groups;
     std::vector<int> group_nodes, blk_group;
+    std::vector<int> node_cps, node_tiles;   // per node: chunks per slab, tiles per side (host only: pleas_gram_batch_plan_info)
     size_t off_nodes = 0, off_items = 0, off_groups = 0, off_gn = 0, off_bg = 0, off_slabs = 0, total = 0;
     int reduce_blocks = 0;
     size_t lds = 0;
@@ -602,6 +620,8 @@ static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, floa
     P.groups.assign(n_groups, GramGroupDev());
     P.group_nodes.clear();
     P.blk_group.clear();
+    P.node_cps.assign(n, 0);
+    P.node_tiles.assign(n, 0);
     P.flops = P.bytes = P.slab_bytes = 0;
     P.lds = 0;
     std::vector<size_t> slab_off(n), spart_off(n);
@@ -643,6 +663,7 @@ static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, floa
         d.source = nd[i].derived ? nd[i].source : -1;
         d.sums = is_source[i];
         d.ax = nd[i].scale_x; d.bx = nd[i].shift_x; d.ay = nd[i].scale_y; d.by = nd[i].shift_y;
+        P.node_tiles[i] = tiles;
         if (nd[i].derived) {   // no contraction, no slabs: the reduce pass reads the source's
             d.S = 0;
             slab_off[i] = 0;
@@ -650,6 +671,7 @@ static int build_batch_plan(BatchPlan& P, const pleas_gram_node* nd, int n, floa
             continue;
         }
         d.S = S;
+        P.node_cps[i] = cps;
         slab_off[i] = slabs;
         slabs += (size_t)S * ((size_t)C * C + 2 * (size_t)C);
         spart_off[i] = slabs;
@@ -744,6 +766,24 @@ extern "C" size_t pleas_gram_batch_ws_bytes(const pleas_gram_node* nodes, int n_
     std::vector<float*> acc(n_groups, nullptr);
     if (build_batch_plan(tmp, nodes, n_nodes, acc.data(), group_C, n_groups) != PLEAS_OK) return 0;
     return tmp.total;
+}
+
+extern "C" int pleas_gram_batch_plan_info(const pleas_gram_node* nodes, int n_nodes, const int* group_C, int n_groups, int* info) {
+    if (!nodes || n_nodes <= 0 || !group_C || n_groups <= 0 || !info) return bad_arg("gram_batch_plan_info: empty input");
+    BatchPlan tmp;
+    std::vector<float*> acc(n_groups, nullptr);
+    if (const int rc = build_batch_plan(tmp, nodes, n_nodes, acc.data(), group_C, n_groups); rc != PLEAS_OK) return rc;
+    for (int i = 0; i < n_nodes; ++i) {
+        const GramNodeDev& d = tmp.nodes[i];
+        int* o = info + 6 * i;
+        o[0] = d.variant;
+        o[1] = d.S;
+        o[2] = tmp.node_cps[i];
+        o[3] = tmp.node_tiles[i];
+        o[4] = (int)d.HWp;
+        o[5] = d.sums;
+    }
+    return PLEAS_OK;
 }
 
 extern "C" int pleas_gram_batch(const pleas_gram_node* nodes, int n_nodes, float* const* group_acc, const int* group_C,

@@ -416,6 +416,8 @@ struct NeqPlan {
     size_t off_layers = 0, off_items = 0, off_red = 0, off_slabs = 0, total = 0, lds = 0;
     double flops = 0, flops_exec = 0, bytes = 0;
     int64_t n_copies = 0;
+    std::vector<int> layer_tiles, layer_blocks, layer_copies;   // per layer: tiles per side, contracted block tiles, blocks
+                                                                // left to finalize (host only: pleas_normal_eq_layer_info)
     bool uploaded = false;
 };
 static PlanCache<NeqPlan, 1> g_nplans;
@@ -427,6 +429,9 @@ static int build_neq_plan(NeqPlan& P, const pleas_neq_layer* ly, int n) {
     P.red.clear();
     P.flops = P.flops_exec = P.bytes = 0;
     P.n_copies = 0;
+    P.layer_tiles.assign(n, 0);
+    P.layer_blocks.assign(n, 0);
+    P.layer_copies.assign(n, 0);
     P.lds = 0;
     std::vector<size_t> slab_off(n, 0);
     size_t slabs = 0;
@@ -494,6 +499,9 @@ static int build_neq_plan(NeqPlan& P, const pleas_neq_layer* ly, int n) {
                         ++tiles_done;
                     }
         if (S > 1) slabs += (size_t)slot * S * T * T;
+        P.layer_tiles[i] = tiles;
+        P.layer_blocks[i] = slot;
+        P.layer_copies[i] = (int)copies.size();
         P.flops += (double)d.K * d.K * (double)K;  // the path's work -- lower triangle: half of 2 K^2 P
         // what the grid executes: whole tiles (ragged ones and the diagonal's upper halves included), lag copies left out
         P.flops_exec += 2.0 * (double)tiles_done * T * T * (double)nchunks * kBK;
@@ -534,6 +542,21 @@ extern "C" int pleas_normal_eq_plan_info(const pleas_neq_layer* layers, int n_la
     info[1] = tmp.flops_exec;
     info[2] = (double)std::count_if(tmp.items.begin(), tmp.items.end(), [](const NeqItemDev& it) { return it.layer >= 0; });
     info[3] = (double)tmp.n_copies;
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_normal_eq_layer_info(const pleas_neq_layer* layers, int n_layers, int* info) {
+    if (!layers || n_layers <= 0 || !info) return bad_arg("normal_eq_layer_info: empty layer list");
+    NeqPlan tmp;
+    if (const int rc = build_neq_plan(tmp, layers, n_layers); rc != PLEAS_OK) return rc;
+    for (int i = 0; i < n_layers; ++i) {
+        int* o = info + 5 * i;
+        o[0] = tmp.layers[i].variant;
+        o[1] = tmp.layers[i].S;
+        o[2] = tmp.layer_tiles[i];
+        o[3] = tmp.layer_blocks[i];
+        o[4] = tmp.layer_copies[i];
+    }
     return PLEAS_OK;
 }
 

@@ -336,6 +336,44 @@ class GramBatch(_GroupedLaunch):
         contracts the same device tensors again)."""
         self._flush(accumulate, keep=keep)
 
+    @staticmethod
+    def plan_info(geometries, group_C=None) -> List[dict]:
+        """Host-side facts about the grouped launch of a node list (``pleas_gram_batch_plan_info``; no GPU work, no tensors):
+        per ``(B, C, HW)`` or ``(B, C, HW, group, source)`` -- ``source``: the index of the node a derived node is an affine
+        image of, else ``None`` -- the tile form ``variant`` (0-5) the plan builder picks, the slabs ``S`` of the K axis (0 for
+        a derived node), the chunks per slab, the tiles per side, the padded pixels per sample ``HWp`` and whether the node
+        writes row sums.  Without ``group_C`` every node that names no group gets one of its own."""
+        geometries = [tuple(g) for g in geometries]
+        n = len(geometries)
+        arr = (_lib.GramNode * max(n, 1))()
+        held = (ctypes.c_float * 1)()
+        some = ctypes.addressof(held)      # a derived node's scale / shift: checked for NULL, never read
+        groups = [] if group_C is None else [int(c) for c in group_C]
+        for i, (a, geo) in enumerate(zip(arr, geometries)):
+            a.B, a.C, a.HW = (int(v) for v in geo[:3])
+            src = geo[4] if len(geo) > 4 else None
+            if len(geo) > 3:
+                a.group = int(geo[3])
+            else:
+                a.group = len(groups)
+                groups.append(a.C)
+            if src is not None:
+                a.derived, a.source = 1, int(src)
+                a.scale_x = a.shift_x = a.scale_y = a.shift_y = some
+        gc = (ctypes.c_int * max(len(groups), 1))(*groups)
+        info = (ctypes.c_int * (6 * max(n, 1)))()
+        check(_lib.lib().pleas_gram_batch_plan_info(arr if n else None, n, gc, len(groups), info), "pleas_gram_batch_plan_info")
+        return [{"variant": info[6 * i], "S": info[6 * i + 1], "chunks_per_slab": info[6 * i + 2], "tiles": info[6 * i + 3],
+                 "HWp": info[6 * i + 4], "sums": bool(info[6 * i + 5])} for i in range(n)]
+
+
+def gram_plan_info(B: int, C: int, HW: int, aligned: bool = True) -> dict:
+    """The plan of the single-node entry ``gram_accum`` for a shape (``pleas_gram_plan_info``; no GPU work): tile, floats per
+    load ``vec``, split-K slabs ``S`` and chunks per slab, given whether both operands are 16-byte aligned."""
+    info = (ctypes.c_int * 4)()
+    check(_lib.lib().pleas_gram_plan_info(int(B), int(C), int(HW), int(bool(aligned)), info), "pleas_gram_plan_info")
+    return {"tile": info[0], "vec": info[1], "S": info[2], "chunks_per_slab": info[3]}
+
 
 # ---------------------------------------------------------------------------------------- LAP
 def _square_costs(costs: Sequence[torch.Tensor], min_n: int):
@@ -1476,6 +1514,22 @@ class NormalEqBatch(_GroupedLaunch):
         if pairs:
             check(_lib.lib().pleas_normal_eq_plan_info(self._layer_array(pairs), len(pairs), info), "pleas_normal_eq_plan_info")
         return {"flops": info[0], "flops_executed": info[1], "items": int(info[2]), "blocks_to_finalize": int(info[3])}
+
+    @staticmethod
+    def layer_info(geometries) -> List[dict]:
+        """Host-side facts per layer of a list (``pleas_normal_eq_layer_info``; no GPU work, no tensors): per
+        ``(N, Cin, Hin, Win, KH, KW, stride, pad)`` the tile form ``variant`` (0-3 direct, 6-7 shifted loader, 8-11 lag classes),
+        the slabs ``S`` of the pixel axis, the tiles per side of a block, the block tiles contracted and the blocks left to
+        ``finalize``."""
+        geometries = list(geometries)
+        n = len(geometries)
+        arr = (_lib.NeqLayer * max(n, 1))()
+        for a, geo in zip(arr, geometries):
+            a.N, a.Cin, a.Hin, a.Win, a.KH, a.KW, a.stride, a.pad = (int(v) for v in geo)
+        info = (ctypes.c_int * (5 * max(n, 1)))()
+        check(_lib.lib().pleas_normal_eq_layer_info(arr if n else None, n, info), "pleas_normal_eq_layer_info")
+        return [{"variant": info[5 * i], "S": info[5 * i + 1], "tiles": info[5 * i + 2], "block_tiles": info[5 * i + 3],
+                 "blocks_to_finalize": info[5 * i + 4]} for i in range(n)]
 
 
 def cholesky_solve_batched(As: Sequence[torch.Tensor], Bts: Sequence[torch.Tensor], ridge: float = 0.0) -> torch.Tensor:
