@@ -445,6 +445,50 @@ int pleas_image_resample(const uint8_t* src, const void* plan_dev, const void* p
                          const uint8_t* flip, float* dst, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * A CHAIN of two resamplings on uint8 images of mixed sizes: Resize, then a resized crop, then flip and table lookup
+ * (csrc/image.hip; the chain plan and its host executor: csrc/resample_plan.hpp).
+ *
+ * Replaces: Resize(256) -> RandomResizedCrop(224) -> ToTensor -> Normalize on the CPU workers of the train loaders
+ *   (experiments/datasets/interface.py, cub.py, nabird.py, oxford_pets.py, stanford_dogs.py, domainnet.py).  Per sample
+ *     img.resize((W1, H1), BILINEAR).crop((x0, y0, x0+w, y0+h)).resize((Wo, Ho), BILINEAR)
+ *   then the flip, then the table: the bits of Normalize(ToTensor(PIL chain)).
+ * Layout: src, src_offset, lut, flip, dst as pleas_image_resample's.  geom int32 [N][8] per sample: H, W (image), H1, W1 (size
+ *   after the first resize, taken as given: torchvision's Resize rule is the caller's), y0, x0, h, w (box inside H1 x W1).
+ *   mid_u8 (host executor, or NULL): the image between the two resizes, uint8 [h_s][w_s][C] per sample, samples end to end.
+ * Arithmetic: each resize is the one-axis pass of pleas_image_resample, horizontal first, stored as uint8, then vertical; the
+ *   image between the two resizes is uint8 as PIL's is.  Of the first resize only the box is computed: columns x0 .. x0+w and
+ *   rows y0 .. y0+h of the virtual H1 x W1 image, from only the source rows their vertical pass reads.  The second resize reads
+ *   nothing outside the box (torchvision's resized_crop crops first).
+ * Determinism: integer sums, no atomics, every byte of the workspace and every element of dst written once; the plan is a pure
+ *   function of its arguments.
+ * Form: one position-independent blob: a chain header, a stage-1 section (laid out like a plan, with the output width and the
+ *   place in the intermediate per sample) and an ordinary stage-2 plan whose source is the intermediate.  Four launches for the
+ *   batch: rows 1 (src -> scratch [rows_s][w_s][C]), bytes 1 (scratch -> intermediate, no table, no flip; a row is w_s * C
+ *   bytes, one kernel for every C), then the rows and planes kernels of pleas_image_resample on the intermediate.  Workgroups
+ *   take items (sample, first row, rows) with a grid stride.  The two scratches and the intermediate are three regions of ws,
+ *   each on a 16-byte boundary, at 64-bit offsets the plan holds.
+ * Limits: as pleas_image_resample's, with H1, W1 among the sides of at most 16384.  The kernels index with nothing that does
+ *   not come from the plan: hand pleas_image_resample_chain the device copy of the plan whose host copy it checks.
+ * pleas_resample_chain_plan_bytes: bytes of the chain plan of geom (0 and a message when geom is refused).
+ *   pleas_resample_chain_plan: writes it into caller memory (4-byte aligned).  pleas_resample_chain_plan_info: info[0 .. 10] =
+ *   N, C, Ho, Wo, bytes of src, bytes of the workspace, bytes of the intermediate, items of rows 1, bytes 1, rows 2, planes 2.
+ *   pleas_image_resample_chain_host: executes a chain plan on the CPU, launch by launch and item by item as the kernels do
+ *   (dst_u8, or NULL: the final bytes [N][Ho][Wo][C] after the flip).  These four touch no device.
+ * PLEAS_EINVAL, before anything is written or enqueued: a box outside H1 x W1; a non-positive size; a side (H, W, H1, W1, Ho,
+ *   Wo) above 16384; C outside 1 .. 4; a sample whose src_offset + H * W * C exceeds src_bytes or is negative; plan memory that
+ *   is NULL, unaligned or too small; a host plan without the magic word, longer than plan_bytes or with a damaged header or
+ *   section; a NULL src, plan, lut or dst with N > 0; a dst that is not 16-byte aligned.  A workspace below the plan's:
+ *   PLEAS_ENOMEM.  N == 0: PLEAS_OK, nothing is enqueued. */
+size_t pleas_resample_chain_plan_bytes(const int32_t* geom, int64_t N, int Ho, int Wo);
+int pleas_resample_chain_plan(const int32_t* geom, const int64_t* src_offset, int64_t N, int C, int Ho, int Wo, int64_t src_bytes,
+                              void* plan, size_t plan_bytes);
+int pleas_resample_chain_plan_info(const void* plan, size_t plan_bytes, int64_t* info);
+int pleas_image_resample_chain_host(const uint8_t* src, const void* plan, size_t plan_bytes, const float* lut, const uint8_t* flip,
+                                    float* dst_f32, uint8_t* dst_u8, uint8_t* mid_u8);
+int pleas_image_resample_chain(const uint8_t* src, const void* plan_dev, const void* plan_host, size_t plan_bytes, const float* lut,
+                               const uint8_t* flip, float* dst, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * PLeaS layer fitting: fused target/residual/loss pass and grouped weight-gradient launch.
  *
  * Replaces, for merging='perm_gradmask': the output half of get_model_orig_activations

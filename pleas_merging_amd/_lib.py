@@ -64,6 +64,12 @@ SIGNATURES = {
     "pleas_image_resample_host": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pleas_image_resample": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
+    "pleas_resample_chain_plan_bytes": (c_size_t, [c_void_p, c_int64, c_int, c_int]),
+    "pleas_resample_chain_plan": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_size_t]),
+    "pleas_resample_chain_plan_info": (c_int, [c_void_p, c_size_t, POINTER(c_int64)]),
+    "pleas_image_resample_chain_host": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pleas_image_resample_chain": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
     "pleas_prof_enable": (None, [c_int]),
     "pleas_prof_select": (None, [ctypes.c_uint]),
     "pleas_prof_reset": (None, []),

@@ -93,6 +93,9 @@ __global__ __launch_bounds__(kImgThreads) void image_batch_kernel(const uint8_t*
 // from the plan's table with a grid stride, so samples of very different sizes share the grid by their rows; inside an item
 // the 256 threads form `by` teams of `bx` lanes as in image_batch_kernel: a team takes a row, its lanes run along x side by
 // side (4-byte runs into each plane of dst).  Everything indexed with comes from the plan, which the host validated.
+//
+// pleas_image_resample_chain (at the end of this file) runs two such resamplings in a row: a ragged form of the rows kernel and
+// resample_bytes_kernel make the uint8 image between them, then the two kernels above run on it.
 constexpr int kResMaxBlocks = 8192;
 constexpr int kResStep = 4;               // outputs of a row per lane of its team (bx = the power of two at or above Wo / 4)
 
@@ -101,19 +104,29 @@ typedef __attribute__((address_space(1))) uint8_t gu8;
 __device__ __forceinline__ int64_t plan64(gcint* p) { return (int64_t)(uint32_t)p[0] | ((int64_t)p[1] << 32); }
 __device__ __forceinline__ int clip8_dev(int v) { return min(max(v >> resample::kPrecisionBits, 0), 255); }
 
-template <int C>
+// the team of a row of `outputs` elements, kResStep to a lane: log2 of the power of two at or above outputs / kResStep, at most 8
+__device__ __forceinline__ int team_log(int outputs) {
+    const int lanes = (outputs + kResStep - 1) / kResStep;
+    return lanes <= 1 ? 0 : min(32 - __clz(lanes - 1), 8);
+}
+
+// kRagged = false: the rows pass of a plan, every sample Wo = the header's wide, teams of 1 << log_bx lanes.
+// kRagged = true: the rows pass of a chain's stage-1 section, sample s its own kSWo wide, the team sized per item from it.
+template <int C, bool kRagged>
 __global__ __launch_bounds__(kImgThreads) void resample_rows_kernel(const uint8_t* __restrict__ src_, const int32_t* __restrict__ plan_,
                                                                     uint8_t* __restrict__ ws_, int log_bx) {
     using namespace resample;
     gcint* plan = PLEAS_GLOBAL_I(plan_);
     gcu8* src = (gcu8*)src_;
     gu8* ws = (gu8*)ws_;
-    const int bx = 1 << log_bx, by = kImgThreads >> log_bx;
-    const int tx = threadIdx.x & (bx - 1), ty = threadIdx.x >> log_bx;
-    const int Wo = plan[kHWo], items = plan[kHItemsH];
+    const int items = plan[kHItemsH];
     gcint* table = plan + plan[kHOffItemsH];
     for (int it = blockIdx.x; it < items; it += gridDim.x) {
         gcint* sm = plan + plan[kHOffSamples] + (int64_t)table[3 * it] * kSampleWords;
+        const int Wo = kRagged ? sm[kSWo] : plan[kHWo];
+        if (kRagged) log_bx = team_log(Wo);
+        const int bx = 1 << log_bx, by = kImgThreads >> log_bx;
+        const int tx = threadIdx.x & (bx - 1), ty = threadIdx.x >> log_bx;
         const int r0 = table[3 * it + 1], r1 = r0 + table[3 * it + 2];
         gcu8* img = src + plan64(sm + kSSrcLo);
         gu8* rows = ws + plan64(sm + kSWsLo);
@@ -137,6 +150,42 @@ __global__ __launch_bounds__(kImgThreads) void resample_rows_kernel(const uint8_
                 }
 #pragma unroll
                 for (int c = 0; c < C; ++c) out[x * C + c] = (uint8_t)clip8_dev(acc[c]);
+            }
+        }
+    }
+}
+
+// The bytes pass of a chain's stage-1 section: scratch [rows_s][w_s][C] -> intermediate uint8 [h_s][w_s][C].  A row is w_s * C
+// bytes, each the same sum down its column whatever channel it belongs to, so one kernel serves every C; a team's lanes run
+// along the bytes side by side.  No table, no flip: the intermediate is the image PIL would hold between the two resizes.
+__global__ __launch_bounds__(kImgThreads) void resample_bytes_kernel(const uint8_t* __restrict__ ws_, const int32_t* __restrict__ plan_,
+                                                                     uint8_t* __restrict__ mid_) {
+    using namespace resample;
+    gcint* plan = PLEAS_GLOBAL_I(plan_);
+    gcu8* ws = (gcu8*)ws_;
+    gu8* mid = (gu8*)mid_;
+    const int C = plan[kHC], items = plan[kHItemsV];
+    gcint* table = plan + plan[kHOffItemsV];
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        gcint* sm = plan + plan[kHOffSamples] + (int64_t)table[3 * it] * kSampleWords;
+        const int rb = sm[kSWo] * C;      // bytes of a row: at most 4 * 16384
+        const int log_bx = team_log(rb);
+        const int bx = 1 << log_bx, by = kImgThreads >> log_bx;
+        const int tx = threadIdx.x & (bx - 1), ty = threadIdx.x >> log_bx;
+        const int y0 = table[3 * it + 1], y1 = y0 + table[3 * it + 2];
+        gcu8* rows = ws + plan64(sm + kSWsLo);
+        gu8* out = mid + plan64(sm + kSMidLo);
+        gcint* vb = plan + sm[kSOffVB];
+        gcint* vk = plan + sm[kSOffVK];
+        const int ks = sm[kSKsV];
+        for (int y = y0 + ty; y < y1; y += by) {
+            const int lo = vb[2 * y], n = vb[2 * y + 1];
+            gcint* k = vk + (int64_t)y * ks;
+            for (int b = tx; b < rb; b += bx) {
+                gcu8* p = rows + (int64_t)lo * rb + b;
+                int acc = 1 << (kPrecisionBits - 1);
+                for (int j = 0; j < n; ++j) acc += k[j] * (int)p[(int64_t)j * rb];
+                out[(int64_t)y * rb + b] = (uint8_t)clip8_dev(acc);
             }
         }
     }
@@ -281,7 +330,7 @@ extern "C" int pleas_image_resample(const uint8_t* src, const void* plan_dev, co
     const dim3 grid_h((unsigned)std::min(plan[kHItemsH], kResMaxBlocks)), grid_v((unsigned)std::min(plan[kHItemsV], kResMaxBlocks));
     hipStream_t stream = (hipStream_t)stream_;
 #define PLEAS_RESAMPLE_LAUNCH(CH)                                                                                                    \
-    hipLaunchKernelGGL(resample_rows_kernel<CH>, grid_h, dim3(kImgThreads), 0, stream, src, (const int32_t*)plan_dev, (uint8_t*)ws,   \
+    hipLaunchKernelGGL((resample_rows_kernel<CH, false>), grid_h, dim3(kImgThreads), 0, stream, src, (const int32_t*)plan_dev, (uint8_t*)ws,   \
                        log_bx);                                                                                                      \
     hipLaunchKernelGGL(resample_planes_kernel<CH>, grid_v, dim3(kImgThreads), 0, stream, (const uint8_t*)ws,                         \
                        (const int32_t*)plan_dev, lut, flip, dst, log_bx)
@@ -293,5 +342,97 @@ extern "C" int pleas_image_resample(const uint8_t* src, const void* plan_dev, co
     }
 #undef PLEAS_RESAMPLE_LAUNCH
     PLEAS_LAUNCH_CHECK("resample kernels");
+    return PLEAS_OK;
+}
+
+// ---- pleas_image_resample_chain: Resize -> RandomResizedCrop as two PIL resamplings with a uint8 image in between, four launches
+//
+//   rows 1    ws1[s][r][x][c]  = clip8(2^21 + sum_j kh1[x][j] * src_s[row0 + r][lo_x + j][c])       x over the box's w_s columns of the
+//   bytes 1   mid[s][y][x][c]  = clip8(2^21 + sum_j kv1[y][j] * ws1[s][lo_y + j][x][c])             virtual H1 x W1 image, y over its h_s rows
+//   rows 2, planes 2           = the two kernels of pleas_image_resample on mid, under the chain's stage-2 plan
+//
+// Replaces: Resize(256) -> RandomResizedCrop(224) on the CPU workers of the drivers' train loaders
+// (experiments/datasets/interface.py, cub.py, nabird.py, oxford_pets.py, stanford_dogs.py, domainnet.py).
+extern "C" size_t pleas_resample_chain_plan_bytes(const int32_t* geom, int64_t N, int Ho, int Wo) {
+    resample::ChainLayout L;
+    if (const char* e = resample::chain_layout_of(geom, N, Ho, Wo, L)) {
+        bad_arg(e);
+        return 0;
+    }
+    return (size_t)L.words * 4;
+}
+
+extern "C" int pleas_resample_chain_plan(const int32_t* geom, const int64_t* src_offset, int64_t N, int C, int Ho, int Wo,
+                                         int64_t src_bytes, void* plan, size_t plan_bytes) {
+    if (const char* e = resample::build_chain_plan(geom, src_offset, N, C, Ho, Wo, src_bytes, (int32_t*)plan, plan_bytes)) return bad_arg(e);
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_resample_chain_plan_info(const void* plan_, size_t plan_bytes, int64_t* info) {
+    const int32_t* plan = (const int32_t*)plan_;
+    if (const char* e = resample::check_chain_header(plan, plan_bytes)) return bad_arg(e);
+    if (!info) return bad_arg("image_resample_chain: null info");
+    using namespace resample;
+    const int32_t* p1 = plan + plan[kCOff1];
+    const int32_t* p2 = plan + plan[kCOff2];
+    info[0] = plan[kCN], info[1] = plan[kCC], info[2] = plan[kCHo], info[3] = plan[kCWo];
+    info[4] = pair64(plan + kCSrcLo), info[5] = pair64(plan + kCWsLo), info[6] = pair64(plan + kCMidLo);
+    info[7] = p1[kHItemsH], info[8] = p1[kHItemsV], info[9] = p2[kHItemsH], info[10] = p2[kHItemsV];
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_image_resample_chain_host(const uint8_t* src, const void* plan_, size_t plan_bytes, const float* lut,
+                                               const uint8_t* flip, float* dst_f32, uint8_t* dst_u8, uint8_t* mid_u8) {
+    using namespace resample;
+    const int32_t* plan = (const int32_t*)plan_;
+    if (const char* e = check_chain_header(plan, plan_bytes)) return bad_arg(e);
+    if (plan[kCN] == 0) return PLEAS_OK;
+    if (!src || !lut || !dst_f32) return bad_arg("image_resample_chain_host: null src, lut or dst");
+    std::vector<uint8_t> ws((size_t)pair64(plan + kCWsLo));
+    execute_chain(src, plan, lut, flip, dst_f32, dst_u8, ws.data());
+    if (mid_u8) std::memcpy(mid_u8, ws.data() + pair64(plan + kCMidAtLo), (size_t)pair64(plan + kCMidLo));
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_image_resample_chain(const uint8_t* src, const void* plan_dev_, const void* plan_host, size_t plan_bytes,
+                                          const float* lut, const uint8_t* flip, float* dst, void* ws_, size_t ws_bytes, void* stream_) {
+    using namespace resample;
+    const int32_t* plan = (const int32_t*)plan_host;
+    if (const char* e = check_chain_header(plan, plan_bytes)) return bad_arg(e);
+    if (plan[kCN] == 0) return PLEAS_OK;      // nothing to write
+    if (!src || !plan_dev_ || !lut || !dst) return bad_arg("image_resample_chain: null src, plan, lut or dst");
+    if (((uintptr_t)plan_dev_ & 3)) return bad_arg("image_resample_chain: the device plan must be 4-byte aligned");
+    if ((uintptr_t)dst & 15) return bad_arg("image_resample_chain: dst must be 16-byte aligned");
+    const size_t need = (size_t)pair64(plan + kCWsLo);
+    if (!ws_ || ws_bytes < need) return workspace_too_small("image_resample_chain", need);
+    const int32_t* p1 = plan + plan[kCOff1];
+    const int32_t* p2 = plan + plan[kCOff2];
+    const int32_t* dev1 = (const int32_t*)plan_dev_ + plan[kCOff1];
+    const int32_t* dev2 = (const int32_t*)plan_dev_ + plan[kCOff2];
+    uint8_t* ws1 = (uint8_t*)ws_;
+    uint8_t* mid = ws1 + pair64(plan + kCMidAtLo);
+    uint8_t* ws2 = ws1 + pair64(plan + kCWs2AtLo);
+    const int C = plan[kCC], Wo = plan[kCWo];
+    const int lanes = (int)ceil_div(Wo, kResStep);
+    int log_bx = 0;
+    while ((1 << log_bx) < lanes && (1 << log_bx) < kImgThreads) ++log_bx;
+    const dim3 grid_h1((unsigned)std::min(p1[kHItemsH], kResMaxBlocks)), grid_v1((unsigned)std::min(p1[kHItemsV], kResMaxBlocks));
+    const dim3 grid_h2((unsigned)std::min(p2[kHItemsH], kResMaxBlocks)), grid_v2((unsigned)std::min(p2[kHItemsV], kResMaxBlocks));
+    hipStream_t stream = (hipStream_t)stream_;
+#define PLEAS_CHAIN_LAUNCH(CH)                                                                                                       \
+    hipLaunchKernelGGL((resample_rows_kernel<CH, true>), grid_h1, dim3(kImgThreads), 0, stream, src, dev1, ws1, 0);                   \
+    hipLaunchKernelGGL(resample_bytes_kernel, grid_v1, dim3(kImgThreads), 0, stream, (const uint8_t*)ws1, dev1, mid);                \
+    hipLaunchKernelGGL((resample_rows_kernel<CH, false>), grid_h2, dim3(kImgThreads), 0, stream, (const uint8_t*)mid, dev2, ws2,     \
+                       log_bx);                                                                                                      \
+    hipLaunchKernelGGL(resample_planes_kernel<CH>, grid_v2, dim3(kImgThreads), 0, stream, (const uint8_t*)ws2, dev2, lut, flip, dst, \
+                       log_bx)
+    switch (C) {
+        case 1: PLEAS_CHAIN_LAUNCH(1); break;
+        case 2: PLEAS_CHAIN_LAUNCH(2); break;
+        case 3: PLEAS_CHAIN_LAUNCH(3); break;
+        default: PLEAS_CHAIN_LAUNCH(4); break;
+    }
+#undef PLEAS_CHAIN_LAUNCH
+    PLEAS_LAUNCH_CHECK("resample chain kernels");
     return PLEAS_OK;
 }

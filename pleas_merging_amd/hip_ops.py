@@ -2,7 +2,7 @@
 
 PyTorch is used for device memory and streams only: every function here enqueues a
 hand-written gfx950 kernel on torch's current stream via ctypes.  Inputs must be fp32
-CUDA(=HIP) tensors (``image_batch`` / ``image_resample``: uint8 images); anything else raises -- there is no
+CUDA(=HIP) tensors (``image_batch`` / ``image_resample`` / ``image_resample_chain``: uint8 images); anything else raises -- there is no
 eager/CPU fallback.
 """
 from __future__ import annotations
@@ -1198,6 +1198,147 @@ def image_resample(src_u8: torch.Tensor, plan_dev: torch.Tensor, plan: torch.Ten
     check(_lib.lib().pleas_image_resample(src_u8.data_ptr(), plan_dev.data_ptr(), plan.data_ptr(), plan.numel(), table.data_ptr(),
                                           flip.data_ptr() if flip is not None else None, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                           _stream()), "pleas_image_resample")
+    return out
+
+
+RESAMPLE_CHAIN_GEOM = 8      # int32 per sample: H, W, H1, W1, y0, x0, h, w (include/pleas_hip.h)
+
+
+def _resample_chain_geom(geom) -> torch.Tensor:
+    if torch.is_tensor(geom) and geom.is_cuda:
+        raise PleasHipError("image_resample_chain_plan: the geometry is checked on the host: pass a CPU tensor or a sequence")
+    geom = torch.as_tensor(geom)
+    if geom.dtype.is_floating_point or geom.dtype == torch.bool or geom.dim() != 2 or geom.shape[1] != RESAMPLE_CHAIN_GEOM:
+        raise PleasHipError("image_resample_chain_plan: geom must hold integers of shape (N, %d), got %s %s"
+                            % (RESAMPLE_CHAIN_GEOM, geom.dtype, tuple(geom.shape)))
+    if geom.numel() and (int(geom.min()) < -(1 << 31) or int(geom.max()) >= 1 << 31):
+        raise PleasHipError("image_resample_chain_plan: geom does not fit int32")
+    return geom.to(torch.int32).contiguous()
+
+
+def image_resample_chain_plan_bytes(geom, size: Tuple[int, int]) -> int:
+    """Bytes of the chain plan of ``geom`` for outputs of ``size=(Ho, Wo)`` (``pleas_resample_chain_plan_bytes``; refusals raise)."""
+    geom = _resample_chain_geom(geom)
+    n = _lib.lib().pleas_resample_chain_plan_bytes(geom.data_ptr(), geom.shape[0], int(size[0]), int(size[1]))
+    if n == 0:
+        raise PleasHipError("pleas_resample_chain_plan_bytes: %s" % _lib.lib().pleas_last_error().decode())
+    return n
+
+
+def image_resample_chain_plan(geom, src_offset, channels: int, size: Tuple[int, int], src_bytes: int,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The plan of ``image_resample_chain`` for one ragged batch (``pleas_resample_chain_plan``; host only): a uint8 tensor,
+    pinned where a GPU is present, or the leading bytes of ``out`` (as ``image_resample_plan``'s).
+
+    ``geom``: HOST integers [N, 8] per sample -- ``H, W`` (image), ``H1, W1`` (its size after the first resize), ``y0, x0, h, w``
+    (box inside ``H1 x W1``, resampled to ``size=(Ho, Wo)``).  ``src_offset``, ``src_bytes``: as ``image_resample_plan``'s.
+    Everything is validated by the library; a refusal raises ``PleasHipError``."""
+    geom = _resample_chain_geom(geom)
+    n = geom.shape[0]
+    if torch.is_tensor(src_offset) and src_offset.is_cuda:
+        raise PleasHipError("image_resample_chain_plan: offsets are checked on the host: pass a CPU tensor or a sequence")
+    src_offset = torch.as_tensor(src_offset, dtype=torch.int64) if not torch.is_tensor(src_offset) and not len(src_offset) \
+        else torch.as_tensor(src_offset)
+    if src_offset.dtype.is_floating_point or src_offset.dtype == torch.bool or tuple(src_offset.shape) != (n,):
+        raise PleasHipError("image_resample_chain_plan: src_offset must hold %d integers, got %s %s"
+                            % (n, src_offset.dtype, tuple(src_offset.shape)))
+    src_offset = src_offset.to(torch.int64).contiguous()
+    nbytes = image_resample_chain_plan_bytes(geom, size)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8)
+        if torch.cuda.is_available():
+            out = out.pin_memory()
+    elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.is_cuda or not out.is_contiguous() or out.numel() < nbytes
+          or out.data_ptr() % 4):
+        raise PleasHipError("image_resample_chain_plan: out must be a contiguous uint8 host tensor of at least %d bytes on a 4-byte "
+                            "boundary" % nbytes)
+    plan = out.view(-1)[:nbytes]
+    check(_lib.lib().pleas_resample_chain_plan(geom.data_ptr(), src_offset.data_ptr(), n, int(channels), int(size[0]), int(size[1]),
+                                               int(src_bytes), plan.data_ptr(), nbytes), "pleas_resample_chain_plan")
+    return plan
+
+
+def image_resample_chain_plan_info(plan: torch.Tensor) -> dict:
+    """What a HOST chain plan says of itself: ``n, channels, size, src_bytes, ws_bytes, mid_bytes, items`` (the item counts of the
+    four launches; ``pleas_resample_chain_plan_info``)."""
+    if not torch.is_tensor(plan) or plan.dtype != torch.uint8 or plan.is_cuda or not plan.is_contiguous():
+        raise PleasHipError("image_resample_chain: the host plan must be a contiguous uint8 CPU tensor (image_resample_chain_plan's)")
+    info = (ctypes.c_int64 * 11)()
+    check(_lib.lib().pleas_resample_chain_plan_info(plan.data_ptr(), plan.numel(), info), "pleas_resample_chain_plan_info")
+    return {"n": info[0], "channels": info[1], "size": (info[2], info[3]), "src_bytes": info[4], "ws_bytes": info[5],
+            "mid_bytes": info[6], "items": tuple(info[7:11])}
+
+
+def image_resample_chain_host(src_u8: torch.Tensor, plan: torch.Tensor, table: torch.Tensor, flip=None):
+    """A chain plan executed on the CPU, launch by launch as the four kernels do (``pleas_image_resample_chain_host``): returns
+    ``(fp32 [N, C, Ho, Wo], uint8 [N, Ho, Wo, C], uint8 [mid_bytes])`` -- the final bytes through ``table``, the final bytes
+    (both after the flip), and the images between the two resizes, ``[h, w, C]`` per sample, end to end."""
+    info = image_resample_chain_plan_info(plan)
+    n, c, (ho, wo) = info["n"], info["channels"], info["size"]
+    if not torch.is_tensor(src_u8) or src_u8.dtype != torch.uint8 or src_u8.is_cuda or not src_u8.is_contiguous():
+        raise PleasHipError("image_resample_chain_host: src must be a contiguous uint8 CPU tensor")
+    if src_u8.numel() < info["src_bytes"]:
+        raise PleasHipError("image_resample_chain_host: src holds %d bytes, the plan was built for %d" % (src_u8.numel(), info["src_bytes"]))
+    if table.is_cuda or table.dtype != torch.float32 or tuple(table.shape) != (c, 256) or not table.is_contiguous():
+        raise PleasHipError("image_resample_chain_host: table must be a contiguous fp32 [%d, 256] CPU tensor" % c)
+    flip = _resample_flip(flip, n)
+    if flip is not None and flip.is_cuda:
+        raise PleasHipError("image_resample_chain_host: flip flags must be host values")
+    f32, u8 = torch.empty((n, c, ho, wo), dtype=torch.float32), torch.empty((n, ho, wo, c), dtype=torch.uint8)
+    mid = torch.empty(info["mid_bytes"], dtype=torch.uint8)
+    check(_lib.lib().pleas_image_resample_chain_host(src_u8.data_ptr(), plan.data_ptr(), plan.numel(), table.data_ptr(),
+                                                     flip.data_ptr() if flip is not None else None, f32.data_ptr(), u8.data_ptr(),
+                                                     mid.data_ptr()), "pleas_image_resample_chain_host")
+    return f32, u8, mid
+
+
+def image_resample_chain(src_u8: torch.Tensor, plan_dev: torch.Tensor, plan: torch.Tensor, table: torch.Tensor, flip=None,
+                         out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Packed uint8 images of mixed sizes on the GPU to normalised fp32 [N, C, Ho, Wo] through PIL's ``resize -> crop -> resize``
+    chain, flip and table lookup in four launches (``pleas_image_resample_chain``).
+
+    Arguments as ``image_resample``'s, with the plan of ``image_resample_chain_plan``.  The two scratches and the intermediate
+    image come from the stream's ``Workspace``, or from ``scratch``: a contiguous uint8 tensor on src's device of at least the
+    plan's ``ws_bytes`` (every byte read is written first, whatever it held)."""
+    if not torch.is_tensor(src_u8) or src_u8.dtype != torch.uint8:
+        raise PleasHipError("image_resample_chain: src must be a uint8 tensor (got %s)" % getattr(src_u8, "dtype", type(src_u8)))
+    if not src_u8.is_contiguous():
+        raise PleasHipError("image_resample_chain: src must be contiguous (one packed buffer)")
+    info = image_resample_chain_plan_info(plan)
+    n, c, (ho, wo) = info["n"], info["channels"], info["size"]
+    if src_u8.numel() < info["src_bytes"]:
+        raise PleasHipError("image_resample_chain: src holds %d bytes, the plan was built for %d" % (src_u8.numel(), info["src_bytes"]))
+    flip = _resample_flip(flip, n)
+    if out is not None and (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (n, c, ho, wo) or not out.is_contiguous()
+                            or out.data_ptr() % 16):
+        raise PleasHipError("image_resample_chain: out must be a contiguous, 16-byte aligned fp32 tensor of shape %s on the GPU"
+                            % ((n, c, ho, wo),))
+    if not src_u8.is_cuda:
+        raise PleasHipError("HIP path needs tensors on the GPU (got device %s); no CPU fallback" % src_u8.device)
+    dev = src_u8.device
+    _need_gpu(table)
+    if table.device != dev or tuple(table.shape) != (c, 256) or not table.is_contiguous():
+        raise PleasHipError("image_resample_chain: table must be a contiguous fp32 [%d, 256] tensor on src's device" % c)
+    if (not torch.is_tensor(plan_dev) or plan_dev.dtype != torch.uint8 or plan_dev.device != dev or not plan_dev.is_contiguous()
+            or plan_dev.numel() < plan.numel() or plan_dev.data_ptr() % 4):
+        raise PleasHipError("image_resample_chain: plan_dev must be the plan's %d bytes as a contiguous uint8 tensor on src's device, "
+                            "4-byte aligned" % plan.numel())
+    if scratch is not None and (not torch.is_tensor(scratch) or scratch.dtype != torch.uint8 or scratch.device != dev
+                                or not scratch.is_contiguous() or scratch.numel() < info["ws_bytes"]):
+        raise PleasHipError("image_resample_chain: scratch must be a contiguous uint8 tensor of at least %d bytes on src's device"
+                            % info["ws_bytes"])
+    if out is None:
+        out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=dev)
+    elif out.device != dev:
+        raise PleasHipError("image_resample_chain: out must be on src's device")
+    if n == 0:
+        return out
+    if flip is not None and flip.device != dev:
+        flip = flip.to(dev)
+    ws = scratch if scratch is not None else Workspace.get(dev).reserve(info["ws_bytes"])
+    check(_lib.lib().pleas_image_resample_chain(src_u8.data_ptr(), plan_dev.data_ptr(), plan.data_ptr(), plan.numel(), table.data_ptr(),
+                                                flip.data_ptr() if flip is not None else None, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _stream()), "pleas_image_resample_chain")
     return out
 
 

@@ -12,7 +12,9 @@ Decoded images come in every size, and the drivers' loaders resample them per im
 training, ``Resize(256)`` + ``CenterCrop(224)`` for evaluation: experiments/shared_label_space/run_domainnet.py:204-214).  With
 ``collate_fn=ragged_collate`` a loader hands the images over as a list of uint8 ``[H, W, C]`` tensors; ``DeviceImages`` packs
 them, with the plan of ``hip_ops.image_resample``, into one staging buffer and resamples on the GPU in PIL's own integer
-arithmetic, so the batch has the bits the CPU chain would have produced.
+arithmetic, so the batch has the bits the CPU chain would have produced.  The datasets' shared train transform is a chain,
+``Resize(256)`` -> ``RandomResizedCrop(224)`` (experiments/datasets/interface.py): ``pre_resize=`` with ``resized_crop=`` runs
+both resamplings on the GPU through ``hip_ops.image_resample_chain``.
 """
 from __future__ import annotations
 
@@ -76,6 +78,11 @@ class DeviceImages:
                            ``(seed, epoch, batch index)``, the flip flags after all boxes;
       ``resize=s`` + ``crop=(Ho, Wo)``   ``Resize(s)`` (shorter side to ``s``) then ``CenterCrop``: the window is the centre one
                            whatever ``seed`` is (the seed only feeds ``flip``); only the window is computed.
+      ``pre_resize=s`` + ``resized_crop=(Ho, Wo)``   ``Resize(s)`` then ``RandomResizedCrop``, the train transform of most of the
+                           reference's datasets (experiments/datasets/interface.py): two PIL resamplings with an 8-bit image
+                           in between, by ``hip_ops.image_resample_chain``.  The box is drawn on the resized size ``(H1, W1)``
+                           -- shorter side ``s``, longer ``int(s * long / short)`` -- in the order above; only the box of the
+                           first resize is computed.
     The images, the flags and the plan travel in ONE staging buffer and one copy on the "h2d" stream, ``depth`` batches ahead
     as above.  With either argument set, a uniform uint8 ``[N, H, W, C]`` host batch takes the same path (one wrapper, one
     output size); uint8 batches on the device and ``"nchw"`` ones are refused then.  fp32 batches still pass through."""
@@ -83,7 +90,7 @@ class DeviceImages:
     def __init__(self, loader, mean, std, device, layout: str = "nhwc", crop: Optional[Tuple[int, int]] = None,
                  flip: bool = False, seed: Optional[int] = 0, depth: int = 2, resized_crop: Optional[Tuple[int, int]] = None,
                  scale: Tuple[float, float] = (0.08, 1.0), ratio: Tuple[float, float] = (3.0 / 4.0, 4.0 / 3.0),
-                 resize: Optional[int] = None):
+                 resize: Optional[int] = None, pre_resize: Optional[int] = None):
         if layout not in hip_ops.IMAGE_LAYOUTS:
             raise ValueError("DeviceImages: layout must be one of %r, got %r" % (tuple(hip_ops.IMAGE_LAYOUTS), layout))
         if depth < 1:
@@ -100,6 +107,11 @@ class DeviceImages:
             raise ValueError("DeviceImages: scale and ratio must be positive, increasing pairs, got %r %r" % (scale, ratio))
         if resize is not None and int(resize) < 1:
             raise ValueError("DeviceImages: resize must be positive, got %r" % (resize,))
+        if pre_resize is not None and resized_crop is None:
+            raise ValueError("DeviceImages: pre_resize is the Resize in front of resized_crop=(Ho, Wo); Resize + CenterCrop is "
+                             "resize=s with crop=(Ho, Wo)")
+        if pre_resize is not None and int(pre_resize) < 1:
+            raise ValueError("DeviceImages: pre_resize must be positive, got %r" % (pre_resize,))
         self.loader, self.mean, self.std = loader, mean, std
         self.device = torch.device(device)
         self.layout, self.flip, self.seed, self.depth = layout, bool(flip), seed, int(depth)
@@ -107,6 +119,7 @@ class DeviceImages:
         self.resized_crop = None if resized_crop is None else (int(resized_crop[0]), int(resized_crop[1]))
         self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
         self.resize = None if resize is None else int(resize)
+        self.pre_resize = None if pre_resize is None else int(pre_resize)
         self.epoch = 0                  # iter() calls so far
         self._tables = {}               # channels -> device table
         self._staging = [None] * self.depth      # [pinned uint8 buffer, event of the last copy out of it]
@@ -194,6 +207,27 @@ class DeviceImages:
         flags = (torch.rand(n, generator=g) < 0.5).to(torch.uint8) if self.flip else None
         return geom, flags
 
+    def chain_augmentation(self, epoch: int, index: int, sizes: Sequence[Tuple[int, int]]):
+        """``(geom, flip)`` of batch ``index`` of epoch ``epoch`` under ``pre_resize`` + ``resized_crop``: int32 ``[n, 8]``
+        descriptors of ``hip_ops.image_resample_chain_plan`` (``H, W, H1, W1, y0, x0, h, w``), uint8 ``[n]`` or None (no flip).
+        ``(H1, W1)`` is ``Resize(pre_resize)``'s size of the image, the box is drawn on it.  A pure function of ``(seed, epoch,
+        index)`` and the sizes."""
+        if self.pre_resize is None:
+            raise ValueError("DeviceImages: chain_augmentation needs pre_resize=s with resized_crop=(Ho, Wo)")
+        n, s = len(sizes), self.pre_resize
+        g = self._generator(epoch, index)
+        rows = []
+        for height, width in sizes:
+            height, width = int(height), int(width)
+            if width <= height:              # Resize(s): the shorter side becomes s
+                h1, w1 = int(s * height / width), s
+            else:
+                h1, w1 = s, int(s * width / height)
+            rows.append((height, width, h1, w1) + self._box(g, h1, w1))
+        geom = torch.tensor(rows, dtype=torch.int32).reshape(n, hip_ops.RESAMPLE_CHAIN_GEOM)
+        flags = (torch.rand(n, generator=g) < 0.5).to(torch.uint8) if self.flip else None
+        return geom, flags
+
     def _table(self, channels: int) -> torch.Tensor:
         t = self._tables.get(channels)
         if t is None:
@@ -221,7 +255,8 @@ class DeviceImages:
 
     def _start_ragged(self, epoch: int, index: int, items, images):
         """Pack a list of uint8 ``[H, W, C]`` host images, their flip flags and the plan into staging buffer ``index % depth``
-        (plan | flags | images, the first two padded to 16 bytes) and begin its copy."""
+        (plan | flags | images, the first two padded to 16 bytes) and begin its copy.  The plan is the chain's under
+        ``pre_resize``."""
         images = [_as_image(im) for im in images]
         for im in images:
             if not torch.is_tensor(im) or im.dtype != torch.uint8:
@@ -233,19 +268,23 @@ class DeviceImages:
         channels = images[0].shape[2] if images else 3
         if any(im.shape[2] != channels for im in images):
             raise hip_ops.PleasHipError("DeviceImages: the images of a batch must share their channel count")
-        geom, flags = self.ragged_augmentation(epoch, index, [(im.shape[0], im.shape[1]) for im in images])
+        chain = self.pre_resize is not None
+        draw = self.chain_augmentation if chain else self.ragged_augmentation
+        plan_size, plan_of = ((hip_ops.image_resample_chain_plan_bytes, hip_ops.image_resample_chain_plan) if chain else
+                              (hip_ops.image_resample_plan_bytes, hip_ops.image_resample_plan))
+        geom, flags = draw(epoch, index, [(im.shape[0], im.shape[1]) for im in images])
         n, size = len(images), self.out_size
         sizes = [im.numel() for im in images]
         offsets = [0] * n
         for i in range(1, n):
             offsets[i] = offsets[i - 1] + sizes[i - 1]
         src_bytes = sum(sizes)
-        plan_bytes = hip_ops.image_resample_plan_bytes(geom, size)
+        plan_bytes = plan_size(geom, size)
         at_flags = _pad16(plan_bytes)
         at_src = at_flags + _pad16(n)
         slot = index % self.depth
         buf = self._buffer(slot, at_src + src_bytes)
-        plan = hip_ops.image_resample_plan(geom, offsets, channels, size, src_bytes, out=buf)
+        plan = plan_of(geom, offsets, channels, size, src_bytes, out=buf)
         if flags is not None:
             buf[at_flags:at_flags + n].copy_(flags)
         for im, o, nb in zip(images, offsets, sizes):
@@ -280,8 +319,9 @@ class DeviceImages:
         if copy is not None and len(copy) == 4:      # a resampled batch: plan | flags | images in one buffer
             (d, ev, plan, (plan_bytes, at_flags, at_src, src_bytes, n, channels)) = copy
             u8 = hip_ops.h2d_finish(d, ev, self.device)
-            out = hip_ops.image_resample(u8[at_src:at_src + src_bytes], u8[:plan_bytes], plan, self._table(channels),
-                                         flip=None if at_flags is None else u8[at_flags:at_flags + n])
+            resample = hip_ops.image_resample if self.pre_resize is None else hip_ops.image_resample_chain
+            out = resample(u8[at_src:at_src + src_bytes], u8[:plan_bytes], plan, self._table(channels),
+                           flip=None if at_flags is None else u8[at_flags:at_flags + n])
             return (out,) + items[1:]
         if not torch.is_tensor(x) or x.dtype != torch.uint8:
             return (hip_ops.to_device_async(x, self.device),) + items[1:]
