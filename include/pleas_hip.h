@@ -621,6 +621,67 @@ int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, void* ws, s
 int pleas_wgrad_plan_info(const pleas_wgrad_layer* layers, int n_layers, int* info);
 
 /* ------------------------------------------------------------------------------------
+ * Depthwise convolutions (nn.Conv2d with groups == in_channels == out_channels): csrc/dwconv.hip.
+ *
+ * Replaces: the vendor's grouped convolution under every depthwise layer of the frozen source / twin / evaluation forwards
+ *   (pleas/methods/pleas_merging.py:267-268, activation_matching.py:49-100, the evaluation helpers :469-586), and -- for the fit --
+ *   `layer(ip)`, the MSE and autograd's backward of such a layer (pleas_merging.py:281-287), which the library ran on the vendor's
+ *   operators one layer at a time.
+ * Layout: x [N][C][Hin][Win], w [C][1][K][K], y / z / res [N][C][Ho][Wo], Ho = (Hin + 2 pad - K) / stride + 1; bias, scale, shift
+ *   fp32[C].  Only the tensor BASES must be 16-byte aligned (bias / scale / shift: 4-byte): rows of any width are legal.
+ * Arithmetic: fp32, plain FMA, the same code under every pleas_arith mode.
+ *   pleas_dwconv2d_fwd:  y = dwconv(x, w) (+ bias), stored when y != NULL;  z = act(fma(y, scale[c], shift[c]) (+ res)), stored
+ *     when z != NULL -- bit for bit what pleas_bn_act makes of the stored y (scale == NULL: z = act(y (+ res))).  The three uses
+ *     are y alone (pleas_conv2d_fwd), y and z (pleas_conv2d_bn_act_fwd) and z alone (pleas_conv2d_act_fwd).
+ *   pleas_dw_fwd_batch: per layer the contract of pleas_fwd_batch -- out = dwconv(ip, w) (+ bias) is never stored; tgt from o1, o2,
+ *     row1, row2, n_merged as there; resid = dscale * (out - tgt) stored; loss[i] = loss_scale * sum (out - tgt)^2.  This kernel
+ *     alone accumulates in fp64 (the forward's chain and order, every fp32 product exact): a residual and a loss are each rounded
+ *     to fp32 once, which is what keeps the loss of a layer with a single output within 2^-24 of the fp64 value.
+ *   pleas_dw_wgrad_batch: grad[c][ky][kx] = sum_{n,oy,ox} resid[n][c][oy][ox] * ip[n][c][oy*stride+ky-pad][ox*stride+kx-pad]  (the
+ *     bias gradient stays with pleas_channel_sum).
+ * Determinism: no atomics, every output element written once, one stated summation order per kernel (header of csrc/dwconv.hip):
+ *   forward -- taps ky outer, kx inner, ascending, one fmaf chain from 0, taps outside the image times 0, bias last; loss --
+ *   per-workgroup partials, then one ordered pass; gradient -- per (channel, slab of output rows) K*K partial sums, then the slabs
+ *   in order, the slab split a function of the geometry alone.  Grouped and alone give the same bits.
+ * Form: a thread owns one output column of a strip of 4 output rows of one (n, c) plane and walks the strip's input rows once;
+ *   lanes run along the row, then over strips and planes; the channel's K*K weights sit in registers.
+ * Limits: K odd in 1 .. 7, stride 1 or 2, pad <= K / 2, square kernel / stride / padding; every per-call element count (input,
+ *   output, a source output) below 2^30.
+ * EINVAL (before anything is enqueued): NULL x or w; both y and z NULL; scale without shift (or the reverse); scale / shift / res
+ *   without z; non-positive sizes (a kernel larger than the padded image included); even K or K > 7; a stride outside {1, 2};
+ *   pad > K / 2; a misaligned base pointer; an element count at or above 2^30; grouped: an empty list, a NULL pointer of a layer
+ *   (bias excepted), N <= 0, n_merged outside 0 .. C.  N == 0 (pleas_dwconv2d_fwd): PLEAS_OK, nothing is enqueued.  A workspace
+ *   that is NULL or smaller than the *_ws_bytes answer: PLEAS_ENOMEM.  *_ws_bytes returns 0 (message in pleas_last_error) for a
+ *   list the launch would refuse on its geometry; it reads no pointer of a layer.  ws / ws_fresh as in pleas_gram_batch. */
+int pleas_dwconv2d_fwd(const float* x, const float* w, const float* bias, float* y, const float* scale, const float* shift,
+                       const float* res, float* z, int relu, int N, int C, int Hin, int Win, int K, int stride, int pad,
+                       void* stream);
+typedef struct pleas_dw_layer {
+    const float* ip;     /* [N][C][Hin][Win] merged input */
+    const float* w;      /* [C][1][K][K] */
+    const float* bias;   /* [C] or NULL */
+    const float* o1;     /* [N][Csrc][Ho*Wo] source-layer outputs */
+    const float* o2;
+    const int32_t* row1; /* [C] block maps (DEVICE), -1 = absent */
+    const int32_t* row2;
+    float* resid;        /* [N][C][Ho*Wo] */
+    int N, C, Hin, Win, K, stride, pad, Csrc, n_merged;
+    float dscale, loss_scale;
+} pleas_dw_layer;
+size_t pleas_dw_fwd_batch_ws_bytes(const pleas_dw_layer* layers, int n_layers);
+int pleas_dw_fwd_batch(const pleas_dw_layer* layers, int n_layers, float* loss, void* ws, size_t ws_bytes, int ws_fresh,
+                       void* stream);
+typedef struct pleas_dw_wgrad_layer {
+    const float* resid;  /* [N][C][Ho*Wo] */
+    const float* ip;     /* [N][C][Hin][Win] */
+    float* grad;         /* [C][1][K][K] */
+    int N, C, Hin, Win, K, stride, pad;
+} pleas_dw_wgrad_layer;
+size_t pleas_dw_wgrad_batch_ws_bytes(const pleas_dw_wgrad_layer* layers, int n_layers);
+int pleas_dw_wgrad_batch(const pleas_dw_wgrad_layer* layers, int n_layers, void* ws, size_t ws_bytes, int ws_fresh,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The path's exchange step under data parallelism (no reference counterpart -- the reference is
  * single-GPU): buf[0..n) := sum over the ranks of `comm`, in place, ONE RCCL all-reduce (fp32, sum) enqueued on `stream`.
  * What is exchanged: the flat cost arena of activation matching (all group matrices back to back, ResNet-101: 41 MB) before

@@ -105,6 +105,11 @@ SIGNATURES = {
     "pleas_wgrad_batch_ws_bytes": (c_size_t, [c_void_p, c_int]),
     "pleas_wgrad_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "pleas_wgrad_plan_info": (c_int, [c_void_p, c_int, POINTER(c_int)]),
+    "pleas_dwconv2d_fwd": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_void_p]),
+    "pleas_dw_fwd_batch_ws_bytes": (c_size_t, [c_void_p, c_int]),
+    "pleas_dw_fwd_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "pleas_dw_wgrad_batch_ws_bytes": (c_size_t, [c_void_p, c_int]),
+    "pleas_dw_wgrad_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "pleas_gram_batch_ws_bytes": (c_size_t, [c_void_p, c_int, POINTER(c_int), c_int]),
     "pleas_gram_plan_info": (c_int, [c_int, c_int, c_int64, c_int, POINTER(c_int)]),
     "pleas_gram_batch_plan_info": (c_int, [c_void_p, c_int, POINTER(c_int), c_int, POINTER(c_int)]),
@@ -140,6 +145,20 @@ class WgradLayer(ctypes.Structure):
     _fields_ = [("resid", c_void_p), ("ip", c_void_p), ("grad", c_void_p), ("N", c_int), ("Cout", c_int), ("Cin", c_int),
                 ("Hin", c_int), ("Win", c_int), ("KH", c_int), ("KW", c_int), ("stride", c_int), ("pad", c_int),
                 ("flags", c_int)]
+
+
+class DwLayer(ctypes.Structure):
+    """struct pleas_dw_layer"""
+    _fields_ = [("ip", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("o1", c_void_p), ("o2", c_void_p),
+                ("row1", c_void_p), ("row2", c_void_p), ("resid", c_void_p), ("N", c_int), ("C", c_int), ("Hin", c_int),
+                ("Win", c_int), ("K", c_int), ("stride", c_int), ("pad", c_int), ("Csrc", c_int), ("n_merged", c_int),
+                ("dscale", c_float), ("loss_scale", c_float)]
+
+
+class DwWgradLayer(ctypes.Structure):
+    """struct pleas_dw_wgrad_layer"""
+    _fields_ = [("resid", c_void_p), ("ip", c_void_p), ("grad", c_void_p), ("N", c_int), ("C", c_int), ("Hin", c_int),
+                ("Win", c_int), ("K", c_int), ("stride", c_int), ("pad", c_int)]
 
 
 class GramNode(ctypes.Structure):

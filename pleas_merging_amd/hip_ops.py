@@ -888,6 +888,172 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], strid
     return out
 
 
+# ---------------------------------------------------------------------------------------- depthwise convolutions
+# Who runs a depthwise nn.Conv2d (groups == in_channels == out_channels) of the source / twin / evaluation forwards and of the fit:
+#   "vendor"  the module on the vendor's grouped convolution, the fit by autograd layer by layer: every release so far (the default)
+#   "hip"     csrc/dwconv.hip: ``dwconv2d`` in the forwards, ``DwFwdBatch`` / ``DwWgradBatch`` in the fit
+# ``PLEAS_DEPTHWISE`` in the environment sets the process's form, ``depthwise_form`` a block's.
+DEPTHWISE_FORMS = ("vendor", "hip")
+DW_MAX_KERNEL = 7
+
+
+def _depthwise_form_checked(mode) -> str:
+    if mode not in DEPTHWISE_FORMS:
+        raise ValueError("depthwise form %r is not one of %s" % (mode, DEPTHWISE_FORMS))
+    return mode
+
+
+DEPTHWISE = _depthwise_form_checked(os.environ.get("PLEAS_DEPTHWISE", "vendor"))
+
+
+@contextlib.contextmanager
+def depthwise_form(mode: str):
+    """``DEPTHWISE = mode`` for the block, the previous form again afterwards (also when the block raises).  Process-wide, as
+    ``linear_form``.  Graphs and fitters read the form when they are BUILT."""
+    global DEPTHWISE
+    before, DEPTHWISE = DEPTHWISE, _depthwise_form_checked(mode)
+    try:
+        yield
+    finally:
+        DEPTHWISE = before
+
+
+def dwconv_geometry_ok(k: int, stride: int, pad: int) -> bool:
+    """The geometries of csrc/dwconv.hip: K odd in 1 .. 7, stride 1 or 2, pad <= K // 2."""
+    return 1 <= k <= DW_MAX_KERNEL and k % 2 == 1 and stride in (1, 2) and 0 <= pad <= k // 2
+
+
+def _dw_image(name: str, what: str, t: Optional[torch.Tensor], shape, device) -> Optional[int]:
+    if t is None:
+        return None
+    if (not t.is_cuda or t.device != device or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+            or t.data_ptr() % 16):
+        raise PleasHipError("%s: %s must be a contiguous, 16-byte aligned fp32 tensor of shape %s on the input's device"
+                            % (name, what, tuple(shape)))
+    return t.data_ptr()
+
+
+def _dw_vector(name: str, what: str, t: Optional[torch.Tensor], C: int, device) -> Optional[int]:
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != device or t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous():
+        raise PleasHipError("%s: %s must be a contiguous fp32 tensor of %d elements on the input's device" % (name, what, C))
+    return t.data_ptr()
+
+
+def dwconv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int,
+             scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+             relu: bool = False, out: Optional[torch.Tensor] = None, act_out: Optional[torch.Tensor] = None):
+    """``F.conv2d(x, w, bias, stride, pad, groups=C)`` for a depthwise layer (``pleas_dwconv2d_fwd``): ``x`` [N, C, H, W], ``w``
+    [C, 1, K, K], K odd up to 7, stride 1 or 2, pad <= K // 2; one fmaf chain per output in a fixed order.
+
+    Without ``scale`` / ``act_out``: returns ``y`` (into ``out`` when given).  With ``scale`` and ``shift`` (fp32 [C]): also
+    ``z = act(fma(y, scale, shift) (+ res))``, bit for bit ``bn_act(y, scale, shift, res, relu)``, and returns ``(y, z)``; with
+    ``out=False`` ``y`` is not stored and ``z`` alone is returned (``act_out``: the tensor ``z`` goes to)."""
+    name = "dwconv2d"
+    _need_gpu(x, w)
+    if x.dim() != 4 or not x.is_contiguous() or x.data_ptr() % 16:
+        raise PleasHipError("%s: a contiguous, 16-byte aligned [N, C, H, W] input expected, got %s" % (name, tuple(x.shape)))
+    N, C, H, W = x.shape
+    if w.dim() != 4 or w.shape[0] != C or w.shape[1] != 1 or w.shape[2] != w.shape[3]:
+        raise PleasHipError("%s: a [C, 1, K, K] weight for %d channels expected, got %s" % (name, C, tuple(w.shape)))
+    K = int(w.shape[2])
+    if w.device != x.device or not w.is_contiguous() or w.data_ptr() % 16:
+        raise PleasHipError("%s: the weight must be contiguous, 16-byte aligned and on the input's device" % name)
+    stride, pad = int(stride), int(pad)
+    if not dwconv_geometry_ok(K, stride, pad):
+        raise PleasHipError("%s: K = %d, stride %d, pad %d is outside K odd in 1 .. %d, stride 1 or 2, pad <= K // 2"
+                            % (name, K, stride, pad, DW_MAX_KERNEL))
+    Ho, Wo = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+    if Ho <= 0 or Wo <= 0:
+        raise PleasHipError("%s: a %d x %d kernel does not fit the padded %d x %d image" % (name, K, K, H + 2 * pad, W + 2 * pad))
+    shape, dev = (N, C, Ho, Wo), x.device
+    if (scale is None) != (shift is None):
+        raise PleasHipError("%s: scale and shift come together" % name)
+    image = scale is not None or act_out is not None
+    if not image and (res is not None or relu or out is False):
+        raise PleasHipError("%s: res / relu / out=False need scale and shift (or act_out)" % name)
+    ptrs = (_dw_vector(name, "bias", bias, C, dev), _dw_vector(name, "scale", scale, C, dev), _dw_vector(name, "shift", shift, C, dev),
+            _dw_image(name, "res", res, shape, dev))
+    y = z = None
+    if out is not False:
+        y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+        _dw_image(name, "out", y, shape, dev)
+    if image:
+        z = act_out if act_out is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+        _dw_image(name, "act_out", z, shape, dev)
+    check(_lib.lib().pleas_dwconv2d_fwd(x.data_ptr(), w.data_ptr(), ptrs[0], y.data_ptr() if y is not None else None, ptrs[1], ptrs[2],
+                                        ptrs[3], z.data_ptr() if z is not None else None, int(bool(relu)), N, C, H, W, K, stride, pad,
+                                        _stream()), "pleas_dwconv2d_fwd")
+    if not image:
+        return y
+    return z if y is None else (y, z)
+
+
+class DwFwdBatch(_GroupedLaunch):
+    """Forward + target + residual + loss of the depthwise layers of one update in ONE grouped launch (``pleas_dw_fwd_batch``):
+    ``FwdBatch``'s contract per layer.  ``add`` per layer, ``flush(loss)`` once per update."""
+
+    STRUCT, WS_BYTES, LAUNCH = _lib.DwLayer, "pleas_dw_fwd_batch_ws_bytes", "pleas_dw_fwd_batch"
+
+    def add(self, ip, w, bias, o1, o2, row1, row2, n_merged: int, resid, dscale: float, loss_scale: float,
+            stride: int = 1, pad: int = 0) -> None:
+        for t in (ip, w, o1, o2, resid):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise PleasHipError("DwFwdBatch.add: contiguous fp32 tensors on the GPU expected")
+        if ip.dim() != 4 or w.dim() != 4 or w.shape[0] != ip.shape[1] or w.shape[1] != 1 or w.shape[2] != w.shape[3]:
+            raise PleasHipError("DwFwdBatch.add: ip [N, C, H, W] and w [C, 1, K, K] expected, got %s and %s" % (tuple(ip.shape), tuple(w.shape)))
+        N, C, Hin, Win = ip.shape
+        K = int(w.shape[2])
+        want = (N, C, (Hin + 2 * pad - K) // stride + 1, (Win + 2 * pad - K) // stride + 1)
+        if tuple(resid.shape) != want or o1.shape != o2.shape or o1.dim() != 4 or (o1.shape[0],) + tuple(o1.shape[2:]) != (N,) + want[2:]:
+            raise PleasHipError("DwFwdBatch.add: resid must be %s and o1 / o2 [N, Csrc, Ho, Wo]" % (want,))
+        for r in (row1, row2):
+            if not r.is_cuda or r.dtype != torch.int32 or r.numel() != C or not r.is_contiguous():
+                raise PleasHipError("DwFwdBatch.add: row maps must be contiguous int32 tensors of %d entries on the GPU" % C)
+        if bias is not None and (not bias.is_cuda or bias.dtype != torch.float32 or bias.numel() != C or not bias.is_contiguous()):
+            raise PleasHipError("DwFwdBatch.add: bias must be a contiguous fp32 tensor of %d elements on the GPU" % C)
+        self._queue((ip, w, bias, o1, o2, row1, row2, resid),
+                    (N, C, Hin, Win, K, int(stride), int(pad), o1.shape[1], int(n_merged), float(dscale), float(loss_scale)))
+
+    def _fill(self, a, tensors, geo) -> None:
+        a.ip, a.w, a.bias, a.o1, a.o2, a.row1, a.row2, a.resid = (t.data_ptr() if t is not None else None for t in tensors)
+        a.N, a.C, a.Hin, a.Win, a.K, a.stride, a.pad, a.Csrc, a.n_merged, a.dscale, a.loss_scale = geo
+
+    def _launch_args(self, loss: torch.Tensor) -> tuple:
+        if loss.numel() != len(self._arr) or not loss.is_contiguous() or loss.dtype != torch.float32 or not loss.is_cuda:
+            raise PleasHipError("DwFwdBatch: loss must hold one fp32 value per layer on the GPU")
+        return (loss.data_ptr(),)
+
+    def flush(self, loss: torch.Tensor) -> None:
+        self._flush(loss)
+
+
+class DwWgradBatch(_GroupedLaunch):
+    """Weight gradients of the depthwise layers of one update in ONE grouped launch (``pleas_dw_wgrad_batch``): ``grad`` [C, 1, K, K]
+    from the residual [N, C, Ho, Wo] and the merged input [N, C, H, W]; two stages, fixed order."""
+
+    STRUCT, WS_BYTES, LAUNCH = _lib.DwWgradLayer, "pleas_dw_wgrad_batch_ws_bytes", "pleas_dw_wgrad_batch"
+
+    def add(self, resid: torch.Tensor, ip: torch.Tensor, grad: torch.Tensor, stride: int = 1, pad: int = 0) -> None:
+        for t in (resid, ip, grad):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise PleasHipError("DwWgradBatch.add: contiguous fp32 tensors on the GPU expected")
+        if ip.dim() != 4 or grad.dim() != 4 or grad.shape[0] != ip.shape[1] or grad.shape[1] != 1 or grad.shape[2] != grad.shape[3]:
+            raise PleasHipError("DwWgradBatch.add: ip [N, C, H, W] and grad [C, 1, K, K] expected, got %s and %s"
+                                % (tuple(ip.shape), tuple(grad.shape)))
+        N, C, Hin, Win = ip.shape
+        K = int(grad.shape[2])
+        want = (N, C, (Hin + 2 * pad - K) // stride + 1, (Win + 2 * pad - K) // stride + 1)
+        if tuple(resid.shape) != want:
+            raise PleasHipError("DwWgradBatch.add: resid must be %s, got %s" % (want, tuple(resid.shape)))
+        self._queue((resid, ip, grad), (N, C, Hin, Win, K, int(stride), int(pad)))
+
+    def _fill(self, a, tensors, geo) -> None:
+        a.resid, a.ip, a.grad = (t.data_ptr() for t in tensors)
+        a.N, a.C, a.Hin, a.Win, a.K, a.stride, a.pad = geo
+
+
 # ---------------------------------------------------------------------------------------- Linear
 # Which kernel an nn.Linear the library runs itself goes through (the probe's head, the inference graph's classifier):
 #   "conv"  ``pleas_conv2d_fwd`` with H = W = KH = KW = 1 on 4-D views, and ``channel_sum`` for the bias gradient: the calls and

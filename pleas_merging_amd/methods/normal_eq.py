@@ -36,9 +36,12 @@ class NormalEqFitter(_LayerFitter):
 
     def __init__(self, *args, ridge: float = 1e-6, shard_solve: bool = True, **kwargs):
         super().__init__(*args, **kwargs)
-        if self.vendor_layers:      # the Adam-faithful fitter fits such layers on the vendor's operators; the closed form does not
+        # the Adam-faithful fitter fits such layers on the vendor's operators -- depthwise ones on their own kernels under
+        # depthwise_form("hip") --; the closed form does neither
+        refused = [p.name for p in self.plans if p.name in self.vendor_layers or p.dw]
+        if refused:
             raise NotImplementedError("solver='normal_eq' takes dense, undilated Conv2d layers with a square kernel / stride / "
-                                      "padding; not supported: %s (solver='adam' fits them)" % ", ".join(self.vendor_layers))
+                                      "padding; not supported: %s (solver='adam' fits them)" % ", ".join(refused))
         self.ridge = ridge
         # data parallel: rank r factorises only ITS layers (dealt by K^3, largest first) and the solved parameter arena is
         # summed once over the ranks (the others' layers are zero there): the solve shrinks with the ranks instead of being

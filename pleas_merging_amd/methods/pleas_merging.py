@@ -41,6 +41,7 @@ import contextlib
 import math
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -51,6 +52,7 @@ from .data_parallel import _SPIN, _emulated_collective, _force_collectives, dp_a
 from .frozen_sources import (ActivationTap, FrozenSources, Generation, SourceTaps, TapDict, _TapView,  # noqa: F401
                              prepare_sources, tap_pointers)
 from .partial_matching import block_maps, get_blocks, spread_blocks
+from .source_forward import own_dwconv_ok
 
 
 # ------------------------------------------------------------------------------------------ reference-shaped helpers
@@ -107,7 +109,7 @@ def cosine_lrs(base_lr: float, t_max: int, n: int) -> List[float]:
 
 # ------------------------------------------------------------------------------------------ per-layer plan
 class _LayerPlan:
-    __slots__ = ("name", "mod", "is_conv", "w", "b", "gw", "gb", "gw2", "gb2", "halves", "w_shape", "off_w", "kpos")
+    __slots__ = ("name", "mod", "is_conv", "w", "b", "gw", "gb", "gw2", "gb2", "halves", "w_shape", "off_w", "kpos", "dw")
 
 
 def _identity_block(n: int):
@@ -204,14 +206,17 @@ class _LayerFitter:
         # grouped Conv2d; Linear on inputs with more than two axes) is fitted the way the reference fits EVERY layer
         # (`layer(ip)` under autograd, pleas_merging.py:281-287) on the vendor's operators, layer by layer (_fit_layer_vendor);
         # an update that contains such a layer takes the layer-by-layer path every time ("Layer geometries").
-        self.vendor_layers = [n for n, m in layers.items() if isinstance(m, nn.Conv2d) and not _square_conv(m)]
+        # A depthwise layer (groups == channels) has kernels of its own (csrc/dwconv.hip) under ``hip_ops.depthwise_form("hip")``,
+        # read here, once: it is taken when its planned merged input has as many channels as its weight has rows (``plan.dw``).
         self.layer_modules = layers
         self._lay_out_arenas(sum(_pad4(p.numel()) for m in layers.values() for p in m.parameters()), shard_optimizer)
         self.plans: List[_LayerPlan] = []
         off = 0
         for name, mod in layers.items():
             off = self._plan_layer(name, mod, off, (separate_classifier, model_type, num_classes))
+        self.vendor_layers = [p.name for p in self.plans if p.is_conv and not _square_conv(p.mod) and not p.dw]
         self.wgrad = hip_ops.WgradBatch(self.device)
+        self.dw_wgrad = hip_ops.DwWgradBatch(self.device)
         self.merge = hip_ops.MergeBatch(self.device)
 
     def _lay_out_arenas(self, total: int, shard_optimizer: Optional[bool]) -> None:      # the flat arenas all layers' tensors are views of
@@ -253,6 +258,7 @@ class _LayerFitter:
         bo = self.perm_blocks.get(Axis("%s.weight" % name, 0)) or _identity_block(_fallback_out_width(*fallback))
         cout_src = src.out_channels if plan.is_conv else src.out_features
         plan.halves = half_maps(self.merging, bi, bo, cin, cout_src, dev)
+        plan.dw = bool(plan.is_conv and own_dwconv_ok(mod) and all(im[0].numel() == plan.w_shape[0] for im, _ in plan.halves))
         self.plans.append(plan)
         return off
 
@@ -385,13 +391,18 @@ class _UpdateRecord:
     to repeat it with other tap addresses.  ``_fit_layer`` / ``_fit_layer_vendor`` write here; ``_replay_update`` reads
     nothing else."""
 
-    __slots__ = ("key", "bufs", "names", "fwd_rows", "fwd_loss", "fwd_index", "bias_grads", "vendor_losses", "merge_tab", "fwd_tab", "complete")
+    __slots__ = ("key", "bufs", "names", "fwd_rows", "fwd_loss", "fwd_index", "bias_grads", "vendor_losses", "merge_tab", "fwd_tab", "complete",
+                 "merged", "dw_rows", "dw_loss", "dw_index", "dw_tab", "fwd_pos", "dw_pos")
 
     def __init__(self, key: tuple, bufs: dict):
         self.key, self.bufs = key, bufs    # input shape (_update_key); (layer, half-batch) -> (merged input, residual) of that shape
         # per entry of the grouped forward its plan's index; (residual, plan, bias gradient); vendor layers' (plan index, loss)
         self.fwd_rows, self.bias_grads, self.vendor_losses = [], [], []
+        # depthwise layers: per entry of THEIR grouped forward its plan's index; `merged`: per entry of the grouped merge (dense and
+        # depthwise entries in layer order) its plan's index and whether it is a depthwise one
+        self.dw_rows, self.merged = [], []
         self.names = self.fwd_loss = self.fwd_index = self.merge_tab = self.fwd_tab = None
+        self.dw_loss = self.dw_index = self.dw_tab = self.fwd_pos = self.dw_pos = None
         self.complete = bool(key)          # replayable: every layer went through the grouped launches and their tables agree
 
 
@@ -410,6 +421,7 @@ class PleasFitter(_LayerFitter):
         self.loss_now = self._g_ext[self.p.numel():]                                             # this step, per layer
         self.loss_sum = torch.zeros(len(self.plans), dtype=torch.float32, device=self.device)   # since last report
         self.fwd = self.ops.FwdBatch(self.device)
+        self.dw_fwd = self.ops.DwFwdBatch(self.device)
         # Per input shape: the merged inputs and residuals of every layer live in buffers that are kept between updates
         # (written and read on the update stream only), so the item tables of the three grouped launches change between
         # two updates of that shape in the tap addresses alone -- see _step.
@@ -445,6 +457,9 @@ class PleasFitter(_LayerFitter):
         ops, name, mod, cout = self.ops, plan.name, plan.mod, plan.w_shape[0]
         ip1, ip2 = (t[name] for t in self.gen.taps.inputs)
         o1, o2 = (t[name] for t in self.gen.taps.outputs)
+        if plan.dw:
+            self._fit_layer_depthwise(idx, plan, rec)
+            return
         if not (_square_conv(mod) if plan.is_conv else ip1.dim() == 2):
             self._fit_layer_vendor(idx, plan, rec)
             return
@@ -471,9 +486,34 @@ class PleasFitter(_LayerFitter):
             self.fwd.add(ip, plan.w, plan.b, o1, o2, r1, r2, nm, resid, 2.0 / n, 1.0 / n, *geo,
                          flags=ops.FwdBatch.KPOS_MAJOR if plan.kpos else 0)
             rec.fwd_rows.append(idx)
+            rec.merged.append((idx, False))
             gw, gb = (plan.gw, plan.gb) if h == 0 else (plan.gw2, plan.gb2)   # second half: its own arena, added before the exchange
             # every layer, the 3-channel stem included (its rows are (channel, tap) pairs: "virtual channels", csrc/conv.hip)
             self.wgrad.add(resid, ip, gw, *geo, flags=ops.WgradBatch.KPOS_MAJOR if plan.kpos else 0)
+            if gb is not None:
+                rec.bias_grads.append((resid, plan, gb))
+
+    def _fit_layer_depthwise(self, idx: int, plan: _LayerPlan, rec: _UpdateRecord) -> None:
+        """A depthwise layer under ``depthwise_form("hip")``: its merged input joins the grouped merge like any dense layer's; forward,
+        target, residual and loss go to ``DwFwdBatch``, the weight gradient to ``DwWgradBatch`` (csrc/dwconv.hip)."""
+        name, mod, cout = plan.name, plan.mod, plan.w_shape[0]
+        ip1, ip2 = (t[name] for t in self.gen.taps.inputs)
+        o1, o2 = (t[name] for t in self.gen.taps.outputs)
+        stride, pad = mod.stride[0], mod.padding[0]
+        for h, (in_maps, (r1, r2, nm)) in enumerate(plan.halves):
+            if cout != r1.numel():
+                raise RuntimeError("layer %s: %d merged outputs vs %d target blocks" % (name, cout, r1.numel()))
+            kept = rec.bufs.get((idx, h))
+            ip = self.merge.add(ip1, ip2, 1, *in_maps, out=kept[0] if kept else None)
+            resid = kept[1] if kept else torch.empty((ip.shape[0], cout) + tuple(o1.shape[2:]), dtype=torch.float32, device=ip.device)
+            if kept is None:
+                rec.bufs[(idx, h)] = (ip, resid)
+            n = resid.numel() * len(plan.halves) * self.world    # the mean runs over the full (global, stacked) batch
+            self.dw_fwd.add(ip, plan.w, plan.b, o1, o2, r1, r2, nm, resid, 2.0 / n, 1.0 / n, stride, pad)
+            rec.dw_rows.append(idx)
+            rec.merged.append((idx, True))
+            gw, gb = (plan.gw, plan.gb) if h == 0 else (plan.gw2, plan.gb2)
+            self.dw_wgrad.add(resid, ip, gw, stride, pad)
             if gb is not None:
                 rec.bias_grads.append((resid, plan, gb))
 
@@ -554,35 +594,56 @@ class PleasFitter(_LayerFitter):
                 self._fit_layer(idx, plan, rec)
         self.merge.flush()   # ONE grouped launch: the merged inputs of every layer
         if rec.fwd_rows:     # ONE grouped MFMA launch: forward + target + residual + loss of every merged layer
-            rows = tuple(rec.fwd_rows)
-            if rows not in self._loss_bufs:
-                self._loss_bufs[rows] = (torch.zeros(len(rows), dtype=torch.float32, device=self.device),
-                                         torch.tensor(rows, dtype=torch.long, device=self.device))
-            rec.fwd_loss, rec.fwd_index = self._loss_bufs[rows]
+            rec.fwd_loss, rec.fwd_index = self._loss_buffers(tuple(rec.fwd_rows), rec.fwd_rows)
             self.fwd.flush(rec.fwd_loss)
+        if rec.dw_rows:      # after the dense launch: forward + target + residual + loss of every depthwise layer
+            rec.dw_loss, rec.dw_index = self._loss_buffers(("dw",) + tuple(rec.dw_rows), rec.dw_rows)
+            self.dw_fwd.flush(rec.dw_loss)
         self._scatter_losses(rec)
         self._bias_gradients(rec)
-        n_wgrad = self.wgrad.pending()
+        n_wgrad = self.wgrad.pending() + self.dw_wgrad.pending()
         self.wgrad.flush()   # ONE grouped MFMA launch: weight gradients of every merged layer
+        self.dw_wgrad.flush()   # and one for the depthwise layers
         rec.complete = rec.complete and n_wgrad > 0
         if rec.complete:
-            rec.names = tuple(self.plans[i].name for i in rec.fwd_rows)
-            rec.merge_tab, rec.fwd_tab = self.merge.table(), self.fwd.table()
-            rec.complete = (rec.merge_tab is not None and rec.fwd_tab is not None
-                            and len(rec.merge_tab) == len(rec.fwd_tab) == len(rec.names))
+            rec.names = tuple(self.plans[i].name for i, _ in rec.merged)
+            rec.fwd_pos = np.array([k for k, (_, dw) in enumerate(rec.merged) if not dw], dtype=np.intp)
+            rec.dw_pos = np.array([k for k, (_, dw) in enumerate(rec.merged) if dw], dtype=np.intp)
+            rec.merge_tab = self.merge.table()
+            rec.fwd_tab = self.fwd.table() if rec.fwd_rows else None
+            rec.dw_tab = self.dw_fwd.table() if rec.dw_rows else None
+            rows = lambda tab, want: (tab is not None and len(tab) == len(want)) if want else True
+            rec.complete = (rec.merge_tab is not None and len(rec.merge_tab) == len(rec.names)
+                            and rows(rec.fwd_tab, rec.fwd_rows) and rows(rec.dw_tab, rec.dw_rows))
         return rec
+
+    def _loss_buffers(self, key: tuple, rows: list) -> Tuple[torch.Tensor, torch.Tensor]:
+        if key not in self._loss_bufs:
+            self._loss_bufs[key] = (torch.zeros(len(rows), dtype=torch.float32, device=self.device),
+                                    torch.tensor(rows, dtype=torch.long, device=self.device))
+        return self._loss_bufs[key]
 
     def _replay_update(self, rec: _UpdateRecord, ptrs: list) -> None:
         """The recorded launches again on this update's taps: ``ptrs`` = addresses of both models' inputs, then of their outputs."""
-        rec.merge_tab["w1"][:], rec.merge_tab["w2"][:], rec.fwd_tab["o1"][:], rec.fwd_tab["o2"][:] = ptrs
+        rec.merge_tab["w1"][:], rec.merge_tab["w2"][:] = ptrs[0], ptrs[1]
+        if rec.fwd_rows:
+            rec.fwd_tab["o1"][:], rec.fwd_tab["o2"][:] = ptrs[2][rec.fwd_pos], ptrs[3][rec.fwd_pos]
+        if rec.dw_rows:
+            rec.dw_tab["o1"][:], rec.dw_tab["o2"][:] = ptrs[2][rec.dw_pos], ptrs[3][rec.dw_pos]
         with self.ops.pin_stream():
             self.merge.relaunch()
-            self.fwd.relaunch(rec.fwd_loss)
+            if rec.fwd_rows:
+                self.fwd.relaunch(rec.fwd_loss)
+            if rec.dw_rows:
+                self.dw_fwd.relaunch(rec.dw_loss)
         self.fast_updates += 1
         self._scatter_losses(rec)
         self._bias_gradients(rec)
         with self.ops.pin_stream():
-            self.wgrad.relaunch()
+            if rec.fwd_rows:
+                self.wgrad.relaunch()
+            if rec.dw_rows:
+                self.dw_wgrad.relaunch()
 
     def _scatter_losses(self, rec: _UpdateRecord) -> None:
         """Per-layer losses of this update into ``loss_now`` (the gradient arena's tail)."""
@@ -592,8 +653,15 @@ class PleasFitter(_LayerFitter):
                 self.loss_now.index_add_(0, rec.fwd_index, rec.fwd_loss)
             else:
                 self.loss_now.index_copy_(0, rec.fwd_index, rec.fwd_loss)
+        if rec.dw_rows:             # the depthwise layers' grouped forward, at their layers' indices
+            if self.stacked:
+                if not rec.fwd_rows:
+                    self.loss_now.zero_()
+                self.loss_now.index_add_(0, rec.dw_index, rec.dw_loss)
+            else:
+                self.loss_now.index_copy_(0, rec.dw_index, rec.dw_loss)
         if rec.vendor_losses:       # layers fitted on the vendor's operators (_fit_layer_vendor)
-            if not rec.fwd_rows:
+            if not rec.fwd_rows and not rec.dw_rows:
                 self.loss_now.zero_()
             seen = set()
             for idx, loss in rec.vendor_losses:

@@ -17,6 +17,8 @@ be fused.  ``fuse_bn_act`` rewrites an fx trace of the model:
 
     Conv2d (k x k, dense, undilated)   =>  HipConv(conv)(x): ``hip_ops.conv2d`` -- the grouped forward's tile forms as a plain
                                            convolution, bit-for-bit repeatable (``SOURCE_CONV``)
+    Conv2d (depthwise, eval mode)      =>  the same three callables on ``hip_ops.dwconv2d`` under ``hip_ops.depthwise_form("hip")``
+                                           (``own_dwconv_ok``); the module on the vendor's kernel otherwise
     HipConv(conv)(x) -> bn_act(...)    =>  HipConvBnAct: ONE launch that stores the convolution's output (the hooks' tensor) and
                                            its activated image from the same registers (``SOURCE_CONV_BN``)
 
@@ -69,6 +71,22 @@ def own_conv_ok(mod: nn.Module, mode: Optional[str] = None) -> bool:
     return mod.weight.dtype == torch.float32 and k * k <= 64 and (k > 1 or mode == "all")
 
 
+def own_dwconv_ok(mod: nn.Module) -> bool:
+    """Does ``mod`` go through ``hip_ops.dwconv2d``?  Under ``hip_ops.depthwise_form("hip")`` only: a plain ``nn.Conv2d`` with
+    ``groups == in_channels == out_channels`` (one filter per channel), zeros padding, no dilation, fp32, a square odd kernel up to
+    7 x 7, one stride of 1 or 2 and one padding of at most K // 2 for both axes (csrc/dwconv.hip).  A one-channel layer
+    (``groups == 1``) is a dense layer: ``own_conv_ok`` has it."""
+    if hip_ops.DEPTHWISE != "hip" or type(mod) is not nn.Conv2d:
+        return False
+    if not (mod.groups == mod.in_channels == mod.out_channels and mod.groups > 1 and mod.weight.dim() == 4 and mod.weight.shape[1] == 1
+            and mod.weight.shape[0] == mod.groups and mod.padding_mode == "zeros" and isinstance(mod.padding, tuple)
+            and mod.dilation == (1, 1) and mod.weight.dtype == torch.float32):
+        return False
+    if not (mod.stride[0] == mod.stride[1] and mod.padding[0] == mod.padding[1] and mod.kernel_size[0] == mod.kernel_size[1]):
+        return False
+    return hip_ops.dwconv_geometry_ok(mod.kernel_size[0], mod.stride[0], mod.padding[0])
+
+
 def _own_input(x, w, dims: int = 4):
     """``x``, made contiguous, when the library's own kernel takes this call -- a CUDA fp32 tensor of ``dims`` dimensions, the weight on
     the GPU, no autograd; None otherwise (the caller then runs the module)."""
@@ -76,6 +94,11 @@ def _own_input(x, w, dims: int = 4):
             or (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
         return None
     return x if x.is_contiguous() else x.contiguous()
+
+
+def _aligned16(x):
+    """``x``, or a copy of it when its first element is not 16-byte aligned (a slice of a larger tensor)."""
+    return x.clone() if x.data_ptr() % 16 else x
 
 
 def _fire_hooks(mod: nn.Module, x, y):
@@ -97,7 +120,8 @@ class HipConv:
     def __init__(self, conv: nn.Conv2d, tag: str, fire_hooks: bool = True):
         self.conv, self.fire_hooks = conv, fire_hooks
         self.k, self.stride, self.pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        self.kpos = self.k > 1 and conv.weight.shape[1] % 32 == 0
+        self.dw = conv.groups > 1      # a depthwise layer (``own_dwconv_ok``): ``hip_ops.dwconv2d``, the weight as it is
+        self.kpos = not self.dw and self.k > 1 and conv.weight.shape[1] % 32 == 0
         self._w = self._stamp = None
         self.__name__ = self.__qualname__ = "hip_conv_%s" % tag
 
@@ -115,7 +139,10 @@ class HipConv:
         xc = _own_input(x, conv.weight)
         if xc is None:
             return conv(x)                      # the module's own path, hooks included
-        y = hip_ops.conv2d(xc, self.weight(), conv.bias, self.stride, self.pad, self.kpos)
+        if self.dw:
+            y = hip_ops.dwconv2d(_aligned16(xc), self.weight(), conv.bias, self.stride, self.pad)
+        else:
+            y = hip_ops.conv2d(xc, self.weight(), conv.bias, self.stride, self.pad, self.kpos)
         if self.fire_hooks and conv._forward_hooks:
             y, _ = _fire_hooks(conv, x, y)
         return y
@@ -149,7 +176,10 @@ class HipConvBnAct:
         xc = self._fused_input(x, scale, res)
         if xc is None:
             return _bn_act(own(x), scale, shift, res, relu)
-        y, z = hip_ops.conv2d_bn_act(xc, own.weight(), conv.bias, own.stride, own.pad, own.kpos, scale, shift, res, relu)
+        if own.dw:
+            y, z = hip_ops.dwconv2d(_aligned16(xc), own.weight(), conv.bias, own.stride, own.pad, scale, shift, res, relu)
+        else:
+            y, z = hip_ops.conv2d_bn_act(xc, own.weight(), conv.bias, own.stride, own.pad, own.kpos, scale, shift, res, relu)
         if own.fire_hooks and conv._forward_hooks:
             y, replaced = _fire_hooks(conv, x, y)
             if replaced:
@@ -169,6 +199,8 @@ class HipConvAct(HipConvBnAct):
         xc = None if own.fire_hooks and conv._forward_hooks else self._fused_input(x, scale, res)
         if xc is None:
             return super().__call__(x, scale, shift, res, relu)
+        if own.dw:
+            return hip_ops.dwconv2d(_aligned16(xc), own.weight(), conv.bias, own.stride, own.pad, scale, shift, res, relu, out=False)
         return hip_ops.conv2d_act(xc, own.weight(), conv.bias, own.stride, own.pad, own.kpos, scale, shift, res, relu)
 
 
@@ -417,11 +449,13 @@ class HipConvBnStats:
         return self.fused(xc, own.weight(), conv.bias, own.stride, own.pad, own.kpos, parts)
 
 
-def _own_convs(graph: torch.fx.Graph, mods, conv: Optional[str]) -> int:
-    """Every Conv2d call that ``own_conv_ok`` takes becomes a ``HipConv`` call; returns how many."""
+def _own_convs(graph: torch.fx.Graph, mods, conv: Optional[str], depthwise: bool = True) -> int:
+    """Every Conv2d call that ``own_conv_ok`` -- or, with ``depthwise``, ``own_dwconv_ok`` -- takes becomes a ``HipConv`` call;
+    returns how many."""
     swapped = 0
     for node in list(graph.nodes):
-        if node.op == "call_module" and len(node.args) == 1 and not node.kwargs and own_conv_ok(mods.get(node.target), conv):
+        mod = mods.get(node.target) if node.op == "call_module" else None
+        if len(node.args) == 1 and not node.kwargs and (own_conv_ok(mod, conv) or (depthwise and own_dwconv_ok(mod))):
             with graph.inserting_before(node):
                 own = graph.create_node("call_function", HipConv(mods[node.target], node.name), (node.args[0],), {}, name=node.name + "_hip")
             node.replace_all_uses_with(own)
@@ -595,7 +629,8 @@ def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = Fa
     state = BatchesPerForward()                       # train_stats: batches per forwarded tensor, set by the caller
     folded = _fold_chains(graph, mods, op, pool_op, train_stats, state, constants)
     if op is _bn_act and (train_convs or not model.training):
-        folded += _own_convs(graph, mods, conv)
+        # a train-mode graph (the BN-statistics reset) keeps depthwise layers on the module: no statistics epilogue for them
+        folded += _own_convs(graph, mods, conv, depthwise=not model.training)
         if model.training and train_stats:
             _conv_stats_pairs(graph, op, pool_op)
         if not model.training and SOURCE_CONV_BN == "1":

@@ -20,7 +20,7 @@ from torch import nn
 from ..core.utils import Axis
 from .. import hip_ops
 from .source_forward import (BatchesPerForward, HipConv, _foldable, _foldable_train, _train_fold, bn_chain, fold_bn,
-                             own_conv_ok)
+                             own_conv_ok, own_dwconv_ok)
 
 
 def _node(graph: torch.fx.Graph, op: str, target, args=(), name: str = "n") -> torch.fx.Node:
@@ -100,7 +100,7 @@ def _own_conv(twin: torch.fx.Graph, node: torch.fx.Node, side: int, model: nn.Mo
         mod = model.get_submodule(node.target)
     except AttributeError:
         return None
-    if not own_conv_ok(mod):
+    if not (own_conv_ok(mod) or own_dwconv_ok(mod)):      # a depthwise layer: ``hip_ops.dwconv2d`` under ``depthwise_form("hip")``
         return None
     return _node(twin, "call_function", HipConv(mod, "%d_%s" % (side, node.name)), (env[node.args[0]],), "hip_conv")
 
