@@ -207,7 +207,7 @@ int pleas_merge_batch(const pleas_merge_item* items, int n_items, void* ws, size
  *
  * x, res (nullable), y: [n][channels][inner] contiguous fp32;  scale[c] = weight[c] / sqrt(var[c] + eps),
  * shift[c] = bias[c] - mean[c] * scale[c]  (DEVICE, prepared once by the caller).
- *   y = x * scale[c] + shift[c] (+ res);   relu != 0 applies max(., 0).   y must not alias x.
+ *   y = x * scale[c] + shift[c] (+ res);   relu != 0 applies torch.relu's rule: v < 0 -> 0, a NaN stays a NaN.   y must not alias x.
  */
 int pleas_bn_act(const float* x, const float* scale, const float* shift, const float* res, float* y, int64_t n,
                  int channels, int64_t inner, int relu, void* stream);
@@ -230,7 +230,7 @@ int pleas_bn_act_tracked_batches(const float* x, const float* scale, const float
  *   (pleas/methods/pleas_merging.py:267-268 runs the whole model; only Conv2d / Linear inputs and outputs are hooked,
  *   :197-243, so the full-resolution activation between ReLU and the pooling is consumed by nothing and is not written).
  *   y[n][c][oh][ow] = max over the KH x KW window at (oh * stride - pad, ow * stride - pad) of act(x * scale[c] + shift[c]);
- *   out-of-range taps never win (torch pads with -inf), a NaN tap does; floor-mode output size, dilation 1.
+ *   out-of-range taps never win (torch pads with -inf), a NaN tap does, with or without relu; floor-mode output size, dilation 1.
  *   scale == NULL: plain max pooling of x.  y: [n][channels][Ho][Wo], must not alias x. */
 int pleas_bn_act_maxpool(const float* x, const float* scale, const float* shift, float* y, int64_t n, int channels, int H,
                          int W, int KH, int KW, int stride, int pad, int relu, void* stream);
@@ -332,6 +332,36 @@ int pleas_sqerr(const float* a, const float* b, int64_t n, float scale, int accu
 /* Bias gradient of a merged layer: out[c] = sum_{n, p} x[n][c][p] for x = the layer's residual [N][C][HW] (Linear: HW = 1).
  * Replaces the bias node of autograd's backward (pleas_merging.py:287).  Deterministic (fixed order, no atomics). */
 int pleas_channel_sum(const float* x, int N, int C, int64_t HW, float* out, void* stream);
+
+/* Host only (no GPU): the launch shape of a streaming kernel for a geometry -- made by the function its launcher makes it with.
+ * op and its geometry geo[0 .. n_geo):
+ *   PLEAS_STREAM_MERGE_BLOCKS    outer, rows_out, cols_out, inner, rows_src, cols_src, column maps given (0 / 1)
+ *   PLEAS_STREAM_BN_ACT          n, channels, inner, n_per_map (0: one map; pleas_bn_act, _tracked and _tracked_batches)
+ *   PLEAS_STREAM_BN_ACT_MAXPOOL  n, channels, H, W, KH, KW, stride, pad
+ *   PLEAS_STREAM_MASKED_ADAM     n
+ *   PLEAS_STREAM_SQERR           n
+ *   PLEAS_STREAM_TARGET_RESIDUAL N, C, Csrc, HW
+ *   PLEAS_STREAM_CHANNEL_SUM     N, C, HW
+ *   PLEAS_STREAM_POOL_GATHER     N, C, HW, K, channel map given (0 / 1)
+ *   PLEAS_STREAM_TOP1_COUNT      N, C
+ *   PLEAS_STREAM_BN_TRAIN_FOLD   n (samples per batch), batches, channels, inner
+ * aligned: whether every pointer that enters the launch's 16-byte predicate is 16-byte aligned.
+ * info[0] floats per load / store (4 / 1), [1] kernel form (bn_act_maxpool: 0 general, 1 stem; else 0), [2] workgroups (0: the
+ * launch enqueues nothing), [3] threads per workgroup, [4] sweeps = ceil(work items / what one pass of the grid covers) of the
+ * grid-stride loop -- channel_sum and bn_train_fold have none: the trips of a thread's loop over one (sample, channel) slab --,
+ * [5] bn_train_fold: S, the sample slabs per channel (else 0).  A geometry the launch refuses is refused with its message. */
+#define PLEAS_STREAM_MERGE_BLOCKS 0
+#define PLEAS_STREAM_BN_ACT 1
+#define PLEAS_STREAM_BN_ACT_MAXPOOL 2
+#define PLEAS_STREAM_MASKED_ADAM 3
+#define PLEAS_STREAM_SQERR 4
+#define PLEAS_STREAM_TARGET_RESIDUAL 5
+#define PLEAS_STREAM_CHANNEL_SUM 6
+#define PLEAS_STREAM_POOL_GATHER 7
+#define PLEAS_STREAM_TOP1_COUNT 8
+#define PLEAS_STREAM_BN_TRAIN_FOLD 9
+#define PLEAS_STREAM_OPS 10
+int pleas_stream_plan_info(int op, const int64_t* geo, int n_geo, int aligned, int* info);
 
 /* ------------------------------------------------------------------------------------
  * Forward of an nn.Linear: y[n][c] = bias[c] + sum_k x[n][k] * w[c][k]   (csrc/linear.hip).

@@ -53,6 +53,7 @@ SIGNATURES = {
     "pleas_sqerr": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p, c_float, c_void_p, c_void_p, c_size_t,
                             c_void_p]),
     "pleas_channel_sum": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "pleas_stream_plan_info": (c_int, [c_int, POINTER(c_int64), c_int, c_int, POINTER(c_int)]),
     "pleas_linear_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "pleas_linear_plan_info": (c_int, [c_int64, c_int, c_int, POINTER(c_int)]),
     "pleas_linear_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p]),

@@ -183,6 +183,19 @@ static inline int bn_splits(int64_t n, int channels) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(s, n));
 }
 
+// the shape checks and the grid of pleas_bn_train_fold_batches, also what pleas_stream_plan_info answers: grid (channels, S,
+// batches); `work` = a sample's pieces per channel, so sweeps = the trips of a thread's loop over one (n, c) slab
+int bn_train_stream_plan(int64_t n, int batches, int channels, int64_t inner, bool aligned, StreamPlan& p) {
+    if (n <= 0 || channels <= 0 || inner <= 0 || batches <= 0) return bad_arg("empty batch");
+    if (n >= ((int64_t)1 << 31) || channels > 65535 || batches > 65535) return bad_arg("tensor too large");
+    p.S = bn_splits(n, channels);
+    p.vec = (inner % 4 == 0 && aligned) ? 4 : 1;
+    p.threads = kBnThreads;
+    p.blocks = (unsigned)channels * (unsigned)p.S * (unsigned)batches;
+    p.work = inner / p.vec * p.blocks;
+    return PLEAS_OK;
+}
+
 }  // namespace pleas
 
 using namespace pleas;
@@ -197,14 +210,14 @@ extern "C" int pleas_bn_train_fold_batches(const float* x, int64_t n, int batche
                                            float* running_mean, float* running_var, int64_t* num_batches_tracked,
                                            float* scale, float* shift, void* ws, size_t ws_bytes, void* stream_) {
     if (!x || !scale || !shift) return bad_arg("null pointer");
-    if (n <= 0 || channels <= 0 || inner <= 0 || batches <= 0) return bad_arg("empty batch");
     if ((running_mean == nullptr) != (running_var == nullptr)) return bad_arg("running_mean / running_var: both or neither");
-    if (n >= ((int64_t)1 << 31) || channels > 65535 || batches > 65535) return bad_arg("tensor too large");
+    StreamPlan p;
+    if (const int rc = bn_train_stream_plan(n, batches, channels, inner, ((uintptr_t)x & 15) == 0, p); rc != PLEAS_OK) return rc;
     if (!ws || ws_bytes < (size_t)batches * pleas_bn_train_ws_bytes(n, channels)) return PLEAS_ENOMEM;
     if ((uintptr_t)ws & 7) return bad_arg("workspace must be 8-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
-    const int S = bn_splits(n, channels);
-    const int vec = (inner % 4 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
+    const int S = p.S;
+    const int vec = p.vec == 4 ? 1 : 0;
     ProfScope prof(kProfBnAct, 0.0, (double)batches * n * channels * inner * sizeof(float), stream);
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(channels, S, batches), dim3(kBnThreads), 0, stream, x, (int)n, channels,
                        inner, vec, (double*)ws);

@@ -125,6 +125,24 @@ int bn_fold_tile_partials(const double* tile_part, int tile, uint32_t ptot, uint
                           const float* gamma, const float* beta, double eps, double momentum, float* running_mean, float* running_var,
                           int64_t* num_batches_tracked, float* scale, float* shift, hipStream_t stream);
 
+// ---- launch shape of a streaming kernel (elementwise.hip, bn_train.hip, target_residual in conv.hip): what the launcher
+// computes its grid from AND what the host-only query pleas_stream_plan_info answers -- one function per kernel makes both.
+struct StreamPlan {
+    int vec = 1;          // floats per load / store: 4 (16-byte path) or 1
+    int form = 0;         // where a launcher picks between two kernels (bn_act_maxpool: 0 general, 1 stem)
+    unsigned blocks = 0;  // workgroups; 0: nothing to do, nothing is launched
+    int threads = 256;    // per workgroup
+    int lanes = 1;        // threads that share one work item (64: a wave per row)
+    int64_t work = 0;     // work items the grid strides over (channel_sum / bn_train_fold: one thread's inner loop)
+    int S = 0;            // bn_train_fold: sample slabs per channel
+    int64_t sweeps() const {
+        const int64_t per = (int64_t)blocks * threads / lanes;
+        return per ? ceil_div(work, per) : 0;
+    }
+};
+// the shape checks of the launches live in these too: a refused geometry is refused with one message from either side
+int bn_train_stream_plan(int64_t n, int batches, int channels, int64_t inner, bool aligned, StreamPlan& p);    // bn_train.hip
+int target_residual_stream_plan(int64_t N, int64_t C, int64_t Csrc, int64_t HW, bool aligned, StreamPlan& p);  // conv.hip
 
 // ---- opt-in per-kernel timing with HIP events on the launch stream (pleas_prof_* in the C-ABI)
 enum ProfKernel { kProfGramPartial = 0, kProfGramFinalize, kProfLsap, kProfMergeBlocks, kProfMaskedAdam, kProfSqerr,

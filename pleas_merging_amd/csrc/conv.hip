@@ -794,17 +794,28 @@ extern "C" int pleas_wgrad_batch(const pleas_wgrad_layer* layers, int n_layers, 
     return PLEAS_OK;
 }
 
+// the shape checks and the grid of pleas_target_residual, also what pleas_stream_plan_info answers
+int pleas::target_residual_stream_plan(int64_t N, int64_t C, int64_t Csrc, int64_t HW, bool aligned, StreamPlan& p) {
+    if (N <= 0 || C <= 0 || Csrc <= 0 || HW <= 0) return bad_arg("target_residual: shape");
+    const int64_t total = N * C * HW;
+    if (total >= (1ll << 32)) return bad_arg("target_residual: more than 2^32 elements");
+    p.vec = (HW % 4 == 0 && aligned) ? 4 : 1;
+    p.work = total / p.vec;
+    p.blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(p.work, 256), kTrBlocks));
+    return PLEAS_OK;
+}
+
 extern "C" int pleas_target_residual(const float* out, const float* o1, const float* o2, const int32_t* row1,
                                      const int32_t* row2, int n_merged, int N, int C, int Csrc, int64_t HW, float dscale,
                                      float* resid, float* partials, int* n_partials, void* stream_) {
     if (!out || !o1 || !o2 || !row1 || !row2 || !resid || !partials || !n_partials) return bad_arg("target_residual: null");
-    if (N <= 0 || C <= 0 || Csrc <= 0 || HW <= 0) return bad_arg("target_residual: shape");
+    StreamPlan p;
+    if (const int rc = target_residual_stream_plan(N, C, Csrc, HW, ((((uintptr_t)out | (uintptr_t)o1 | (uintptr_t)o2 | (uintptr_t)resid) & 15) == 0), p);
+        rc != PLEAS_OK) return rc;
     const int64_t total = (int64_t)N * C * HW;
-    if (total >= (1ll << 32)) return bad_arg("target_residual: more than 2^32 elements");
-    const bool vec = HW % 4 == 0 &&
-                     ((((uintptr_t)out | (uintptr_t)o1 | (uintptr_t)o2 | (uintptr_t)resid) & 15) == 0);
-    const int64_t pieces = vec ? total / 4 : total;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(pieces, 256), kTrBlocks));
+    const bool vec = p.vec == 4;
+    const int64_t pieces = p.work;
+    const int blocks = (int)p.blocks;
     *n_partials = blocks;
     hipStream_t stream = (hipStream_t)stream_;
     ProfScope prof(kProfSqerr, 0.0, 4.0 * total * sizeof(float), stream);

@@ -116,9 +116,12 @@ __global__ __launch_bounds__(kEwThreads) void merge_blocks_kernel(
     }
 }
 
+// torch.relu's rule: a NaN stays a NaN (fmaxf(v, 0) would turn it into 0 and a diverged model would be evaluated on zeros)
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
 // ------------------------------------------------------------------------------------------
 // Inference BatchNorm folded to one affine map per channel, optional residual add, optional ReLU:
-//   bn = x[n][c][i] * scale[c] + shift[c];   sum = bn (+ res[n][c][i]);   act = relu ? max(sum, 0) : sum
+//   bn = x[n][c][i] * scale[c] + shift[c];   sum = bn (+ res[n][c][i]);   act = relu ? (sum < 0 ? 0 : sum) : sum
 // One pass over x (and res): replaces the vendor BN + in-place add + in-place ReLU chain (3 kernels, 7 tensor passes)
 // of a frozen source model.  `y_act` is always written; `y_bn` / `y_sum` (nullable) are the intermediate values for
 // callers that track them (activation matching measures every node).  `inner_v` = HW / VEC.
@@ -148,7 +151,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_kernel(const float* __restr
             for (int e = 0; e < 4; ++e) {
                 bn[e] = fmaf(q[e], a, b);
                 sm[e] = bn[e] + r[e];
-                o[e] = relu ? fmaxf(sm[e], 0.f) : sm[e];
+                o[e] = relu ? relu_keep_nan(sm[e]) : sm[e];
             }
             if (y_bn) reinterpret_cast<f32x4*>(y_bn)[idx] = bn;
             if (y_sum) reinterpret_cast<f32x4*>(y_sum)[idx] = sm;
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_kernel(const float* __restr
             const float sm = bn + (res ? res[idx] : 0.f);
             if (y_bn) y_bn[idx] = bn;
             if (y_sum) y_sum[idx] = sm;
-            y[idx] = relu ? fmaxf(sm, 0.f) : sm;
+            y[idx] = relu ? relu_keep_nan(sm) : sm;
         }
     }
 }
@@ -168,7 +171,8 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_kernel(const float* __restr
 //   y[n][c][oh][ow] = max over the window of act(x[n][c][ih][iw] * scale[c] + shift[c]),  padding = -inf (never wins)
 // The full-resolution activation between ReLU and the pooling is never written (nothing between two hooked layers is
 // consumed by the PLeaS loop): x is read once, y is a quarter of it.  scale == NULL: plain max pooling of x.
-// A NaN in the window wins, as in the vendor's pooling kernel.  One thread per output element; the rows a window shares
+// A NaN in the window wins, as in the vendor's pooling kernel -- also under relu: the ReLU here keeps a NaN, as torch.relu
+// does (fmaxf would return its other operand, 0).  One thread per output element; the rows a window shares
 // with the next output row are re-read from L1/L2 by the same workgroup.
 __global__ __launch_bounds__(kEwThreads) void bn_act_pool_kernel(const float* __restrict__ x,
                                                                  const float* __restrict__ scale,
@@ -194,7 +198,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_pool_kernel(const float* __
                 if (iw < 0 || iw >= W) continue;
                 float v = src[ih * W + iw];
                 if (scale) v = fmaf(v, a, b);
-                if (relu) v = fmaxf(v, 0.f);
+                if (relu) v = relu_keep_nan(v);
                 if (v > best || v != v) best = v;
             }
         }
@@ -610,25 +614,147 @@ extern "C" int pleas_prof_collect(int kernel, int64_t* launches, double* total_m
     return PLEAS_OK;
 }
 
+// ------------------------------------------------------------------------------------------ launch shapes (host only)
+// One function per kernel: the shape checks of its launch, then vec / form / grid.  The launchers below call them, and so does
+// pleas_stream_plan_info: the query cannot drift from the launch.  `aligned`: every pointer of the launch's 16-byte predicate is
+// 16-byte aligned (all_aligned16; an absent optional pointer is NULL and counts as aligned).
+template <class... P>
+static inline bool all_aligned16(const P*... ptrs) { return ((0 | ... | (uintptr_t)ptrs) & 15) == 0; }
+
+static int merge_blocks_plan(int64_t outer, int64_t rows_out, int64_t cols_out, int64_t inner, int64_t rows_src, int64_t cols_src,
+                             bool col_maps, bool aligned, StreamPlan& p) {
+    if (outer < 0 || rows_out < 0 || cols_out < 0 || inner <= 0 || rows_src <= 0 || cols_src <= 0)
+        return bad_arg("negative size");
+    if (!col_maps && cols_out != cols_src) return bad_arg("cols_out != cols_src without column maps");
+    const int64_t total = outer * rows_out * cols_out * inner;
+    p.vec = (inner % 4 == 0 && aligned) ? 4 : 1;
+    p.work = total / p.vec;
+    p.blocks = total ? ew_grid(p.work) : 0;
+    return PLEAS_OK;
+}
+
+static int bn_act_plan(int64_t n, int64_t channels, int64_t inner, int64_t n_per_map, bool aligned, StreamPlan& p) {
+    if (n < 0 || channels <= 0 || inner <= 0) return bad_arg("negative size");
+    if (n_per_map < 0 || (n_per_map > 0 && n % n_per_map != 0)) return bad_arg("samples do not split into whole batches");
+    const int64_t total = n * channels * inner;
+    if (total == 0) return PLEAS_OK;
+    if (n * channels >= ((int64_t)1 << 31) || inner >= ((int64_t)1 << 31)) return bad_arg("tensor too large");
+    p.vec = (inner % 4 == 0 && aligned) ? 4 : 1;
+    p.work = total / p.vec;
+    p.blocks = ew_grid(p.work);
+    return PLEAS_OK;
+}
+
+static int bn_act_maxpool_plan(int64_t n, int64_t channels, int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t stride,
+                               int64_t pad, bool aligned, StreamPlan& p) {
+    if (n < 0 || channels <= 0 || H <= 0 || W <= 0) return bad_arg("negative size");
+    if (KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || 2 * pad > KH || 2 * pad > KW)
+        return bad_arg("pooling window: need kernel > 0, stride > 0, 0 <= pad <= kernel / 2");
+    if (H + 2 * pad < KH || W + 2 * pad < KW) return bad_arg("pooling window larger than the padded input");
+    const int64_t Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;     // floor mode
+    const int64_t total = n * channels * Ho * Wo;
+    if (total == 0) return PLEAS_OK;
+    if (n * channels >= ((int64_t)1 << 31) || H * W >= ((int64_t)1 << 31)) return bad_arg("tensor too large");
+    const bool stem = KH == 3 && KW == 3 && stride == 2 && pad == 1 && W % 8 == 0 && total / 4 < ((int64_t)1 << 31) && aligned;
+    p.form = stem ? 1 : 0;
+    p.vec = stem ? 4 : 1;
+    p.work = total / p.vec;
+    p.blocks = ew_grid(p.work);
+    return PLEAS_OK;
+}
+
+static int masked_adam_plan(int64_t n, StreamPlan& p) {
+    if (n < 0) return bad_arg("n < 0 or step < 1");
+    p.work = n;
+    p.blocks = n ? ew_grid(n) : 0;
+    return PLEAS_OK;
+}
+
+static int sqerr_plan(int64_t n, StreamPlan& p) {
+    if (n < 0) return bad_arg("n < 0");
+    p.work = n;
+    p.blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, kEwThreads), kSqBlocks));    // n == 0 still writes out
+    return PLEAS_OK;
+}
+
+// channel_sum has no grid-stride loop: a workgroup per channel, and the KERNEL picks the 16-byte loop by the same predicate
+// (HW % 4 == 0, x aligned).  `work`: the pieces of one sample, so sweeps = the trips of a thread's inner loop per sample.
+static int channel_sum_plan(int64_t N, int64_t C, int64_t HW, bool aligned, StreamPlan& p) {
+    if (N <= 0 || C <= 0 || HW <= 0) return bad_arg("channel_sum: empty tensor");
+    p.vec = (HW % 4 == 0 && aligned) ? 4 : 1;
+    p.work = HW / p.vec * C;
+    p.blocks = (unsigned)C;
+    return PLEAS_OK;
+}
+
+static int pool_gather_plan(int64_t N, int64_t C, int64_t HW, int64_t K, bool has_map, bool aligned, StreamPlan& p) {
+    if (N < 0 || C <= 0 || HW <= 0 || K <= 0) return bad_arg("pool_gather: empty tensor");
+    if (!has_map && K != C) return bad_arg("pool_gather: K != C without a channel map");
+    const int64_t rows = N * K;
+    if (rows == 0) return PLEAS_OK;
+    if (rows >= ((int64_t)1 << 40) || N * C >= ((int64_t)1 << 40)) return bad_arg("pool_gather: tensor too large");
+    p.vec = (HW % 4 == 0 && aligned) ? 4 : 1;
+    p.lanes = 64;
+    p.work = rows;
+    p.blocks = (unsigned)std::min<int64_t>(ceil_div(rows, kEwThreads / 64), (int64_t)1 << 20);
+    return PLEAS_OK;
+}
+
+static int top1_count_plan(int64_t N, int64_t C, StreamPlan& p) {
+    if (N < 0 || C <= 0) return bad_arg("top1_count: empty rows");
+    p.lanes = 64;
+    p.work = N;
+    p.blocks = (unsigned)std::min<int64_t>(ceil_div(N, kEwThreads / 64), kEwMaxBlocks);
+    return PLEAS_OK;
+}
+
+extern "C" int pleas_stream_plan_info(int op, const int64_t* g, int n_geo, int aligned, int* info) {
+    static const int kArgs[PLEAS_STREAM_OPS] = {7, 4, 8, 1, 1, 4, 3, 5, 2, 4};
+    if (!g || !info) return bad_arg("stream_plan_info: null pointer");
+    if (op < 0 || op >= PLEAS_STREAM_OPS || n_geo != kArgs[op]) return bad_arg("stream_plan_info: unknown kernel or wrong geometry length");
+    const bool al = aligned != 0;
+    StreamPlan p;
+    int rc = PLEAS_OK;
+    switch (op) {
+        case PLEAS_STREAM_MERGE_BLOCKS: rc = merge_blocks_plan(g[0], g[1], g[2], g[3], g[4], g[5], g[6] != 0, al, p); break;
+        case PLEAS_STREAM_BN_ACT: rc = bn_act_plan(g[0], g[1], g[2], g[3], al, p); break;
+        case PLEAS_STREAM_BN_ACT_MAXPOOL: rc = bn_act_maxpool_plan(g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], al, p); break;
+        case PLEAS_STREAM_MASKED_ADAM: rc = masked_adam_plan(g[0], p); break;
+        case PLEAS_STREAM_SQERR: rc = sqerr_plan(g[0], p); break;
+        case PLEAS_STREAM_TARGET_RESIDUAL: rc = target_residual_stream_plan(g[0], g[1], g[2], g[3], al, p); break;
+        case PLEAS_STREAM_CHANNEL_SUM: rc = channel_sum_plan(g[0], g[1], g[2], al, p); break;
+        case PLEAS_STREAM_POOL_GATHER: rc = pool_gather_plan(g[0], g[1], g[2], g[3], g[4] != 0, al, p); break;
+        case PLEAS_STREAM_TOP1_COUNT: rc = top1_count_plan(g[0], g[1], p); break;
+        default: rc = bn_train_stream_plan(g[0], (int)std::min<int64_t>(g[1], 1 << 30), (int)std::min<int64_t>(g[2], 1 << 30), g[3], al, p); break;
+    }
+    if (rc != PLEAS_OK) return rc;
+    info[0] = p.vec;
+    info[1] = p.form;
+    info[2] = (int)p.blocks;
+    info[3] = p.threads;
+    info[4] = (int)std::min<int64_t>(p.sweeps(), 0x7fffffff);
+    info[5] = p.S;
+    return PLEAS_OK;
+}
+
 extern "C" int pleas_merge_blocks(const float* w1, const float* w2, float* out, int64_t outer, int rows_out,
                                   int cols_out, int64_t inner, int rows_src, int cols_src, const int32_t* row1,
                                   const int32_t* row2, const int32_t* col1, const int32_t* col2, int n_merged_rows,
                                   void* stream_) {
     if (!w1 || !w2 || !out || !row1 || !row2) return bad_arg("null pointer");
-    if (outer < 0 || rows_out < 0 || cols_out < 0 || inner <= 0 || rows_src <= 0 || cols_src <= 0)
-        return bad_arg("negative size");
     if ((col1 == nullptr) != (col2 == nullptr)) return bad_arg("col1/col2 must both be given or both NULL");
-    if (!col1 && cols_out != cols_src) return bad_arg("cols_out != cols_src without column maps");
-    const int64_t total = outer * rows_out * (int64_t)cols_out * inner;
-    if (total == 0) return PLEAS_OK;
+    StreamPlan p;
+    if (const int rc = merge_blocks_plan(outer, rows_out, cols_out, inner, rows_src, cols_src, col1 != nullptr,
+                                         all_aligned16(w1, w2, out), p); rc != PLEAS_OK) return rc;
+    if (p.blocks == 0) return PLEAS_OK;
+    const int64_t total = p.work * p.vec;
     hipStream_t stream = (hipStream_t)stream_;
-    const bool vec = inner % 4 == 0 && ((((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)out) & 15) == 0);
     ProfScope prof(kProfMergeBlocks, 0.0, 3.0 * total * sizeof(float), stream);
-    if (vec)
-        hipLaunchKernelGGL((merge_blocks_kernel<4>), dim3(ew_grid(total / 4)), dim3(kEwThreads), 0, stream, w1, w2, out,
+    if (p.vec == 4)
+        hipLaunchKernelGGL((merge_blocks_kernel<4>), dim3(p.blocks), dim3(kEwThreads), 0, stream, w1, w2, out,
                            outer, rows_out, cols_out, inner, rows_src, cols_src, row1, row2, col1, col2, n_merged_rows);
     else
-        hipLaunchKernelGGL((merge_blocks_kernel<1>), dim3(ew_grid(total)), dim3(kEwThreads), 0, stream, w1, w2, out,
+        hipLaunchKernelGGL((merge_blocks_kernel<1>), dim3(p.blocks), dim3(kEwThreads), 0, stream, w1, w2, out,
                            outer, rows_out, cols_out, inner, rows_src, cols_src, row1, row2, col1, col2, n_merged_rows);
     PLEAS_LAUNCH_CHECK("merge_blocks_kernel");
     return PLEAS_OK;
@@ -638,22 +764,20 @@ static int bn_act_launch(const float* x, const float* scale, const float* shift,
                          float* y_sum, float* y, int64_t n, int channels, int64_t inner, int relu, void* stream_,
                          int64_t n_per_map = 0) {
     if (!x || !scale || !shift || !y) return bad_arg("null pointer");
-    if (n < 0 || channels <= 0 || inner <= 0) return bad_arg("negative size");
-    if (n_per_map < 0 || (n_per_map > 0 && n % n_per_map != 0)) return bad_arg("samples do not split into whole batches");
+    StreamPlan p;
+    if (const int rc = bn_act_plan(n, channels, inner, n_per_map, all_aligned16(x, y, res, y_bn, y_sum), p); rc != PLEAS_OK)
+        return rc;
+    if (p.blocks == 0) return PLEAS_OK;
     const unsigned rows_per_map = (n_per_map > 0 && n_per_map < n) ? (unsigned)(n_per_map * channels) : 0u;
     const int64_t total = n * channels * inner;
-    if (total == 0) return PLEAS_OK;
-    if (n * channels >= ((int64_t)1 << 31) || inner >= ((int64_t)1 << 31)) return bad_arg("tensor too large");
     hipStream_t stream = (hipStream_t)stream_;
-    const uintptr_t all = (uintptr_t)x | (uintptr_t)y | (uintptr_t)res | (uintptr_t)y_bn | (uintptr_t)y_sum;
-    const bool vec = inner % 4 == 0 && (all & 15) == 0;
     const double passes = 2.0 + (res ? 1.0 : 0.0) + (y_bn ? 1.0 : 0.0) + (y_sum ? 1.0 : 0.0);
     ProfScope prof(kProfBnAct, 0.0, passes * total * sizeof(float), stream);
-    if (vec)
-        hipLaunchKernelGGL((bn_act_kernel<4>), dim3(ew_grid(total / 4)), dim3(kEwThreads), 0, stream, x, scale, shift, res,
+    if (p.vec == 4)
+        hipLaunchKernelGGL((bn_act_kernel<4>), dim3(p.blocks), dim3(kEwThreads), 0, stream, x, scale, shift, res,
                            y_bn, y_sum, y, total / 4, (unsigned)(inner / 4), (unsigned)channels, relu, rows_per_map);
     else
-        hipLaunchKernelGGL((bn_act_kernel<1>), dim3(ew_grid(total)), dim3(kEwThreads), 0, stream, x, scale, shift, res,
+        hipLaunchKernelGGL((bn_act_kernel<1>), dim3(p.blocks), dim3(kEwThreads), 0, stream, x, scale, shift, res,
                            y_bn, y_sum, y, total, (unsigned)inner, (unsigned)channels, relu, rows_per_map);
     PLEAS_LAUNCH_CHECK("bn_act_kernel");
     return PLEAS_OK;
@@ -700,7 +824,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_pool3s2_kernel(const float*
 #pragma unroll
             for (int e = 0; e < 9; ++e) {
                 if (scale) v[e] = fmaf(v[e], a, b);
-                if (relu) v[e] = fmaxf(v[e], 0.f);
+                if (relu) v[e] = relu_keep_nan(v[e]);
             }
             if (q == 0) v[0] = ninf;       // the padding column never wins
 #pragma unroll
@@ -720,23 +844,19 @@ extern "C" int pleas_bn_act_maxpool(const float* x, const float* scale, const fl
                                     int channels, int H, int W, int KH, int KW, int stride, int pad, int relu,
                                     void* stream_) {
     if (!x || !y || (scale && !shift)) return bad_arg("null pointer");
-    if (n < 0 || channels <= 0 || H <= 0 || W <= 0) return bad_arg("negative size");
-    if (KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || 2 * pad > KH || 2 * pad > KW)
-        return bad_arg("pooling window: need kernel > 0, stride > 0, 0 <= pad <= kernel / 2");
-    if (H + 2 * pad < KH || W + 2 * pad < KW) return bad_arg("pooling window larger than the padded input");
+    StreamPlan p;
+    if (const int rc = bn_act_maxpool_plan(n, channels, H, W, KH, KW, stride, pad, all_aligned16(x, y), p); rc != PLEAS_OK)
+        return rc;
+    if (p.blocks == 0) return PLEAS_OK;
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;     // floor mode
     const int64_t total = n * channels * Ho * Wo;
-    if (total == 0) return PLEAS_OK;
-    if (n * channels >= ((int64_t)1 << 31) || (int64_t)H * W >= ((int64_t)1 << 31)) return bad_arg("tensor too large");
     hipStream_t stream = (hipStream_t)stream_;
     ProfScope prof(kProfBnAct, 0.0, ((double)n * channels * H * W + (double)total) * sizeof(float), stream);
-    const bool stem = KH == 3 && KW == 3 && stride == 2 && pad == 1 && W % 8 == 0 && total / 4 < ((int64_t)1 << 31) &&
-                      (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
-    if (stem)
-        hipLaunchKernelGGL(bn_act_pool3s2_kernel, dim3(ew_grid(total / 4)), dim3(kEwThreads), 0, stream, x, scale, shift, y,
+    if (p.form == 1)
+        hipLaunchKernelGGL(bn_act_pool3s2_kernel, dim3(p.blocks), dim3(kEwThreads), 0, stream, x, scale, shift, y,
                            (unsigned)(total / 4), (unsigned)channels, H, W, Ho, relu);
     else
-        hipLaunchKernelGGL(bn_act_pool_kernel, dim3(ew_grid(total)), dim3(kEwThreads), 0, stream, x, scale, shift, y, total,
+        hipLaunchKernelGGL(bn_act_pool_kernel, dim3(p.blocks), dim3(kEwThreads), 0, stream, x, scale, shift, y, total,
                            (unsigned)channels, H, W, Ho, Wo, KH, KW, stride, pad, relu);
     PLEAS_LAUNCH_CHECK("bn_act_pool_kernel");
     return PLEAS_OK;
@@ -753,15 +873,17 @@ extern "C" int pleas_bn_act_tracked_batches(const float* x, const float* scale, 
 extern "C" int pleas_masked_adam(float* p, const float* g, const float* mask, float* m, float* v, int64_t n, float lr,
                                  float b1, float b2, float eps, int step, void* stream_) {
     if (!p || !g || !m || !v) return bad_arg("null pointer");
-    if (n < 0 || step < 1) return bad_arg("n < 0 or step < 1");
-    if (n == 0) return PLEAS_OK;
+    StreamPlan plan;
+    if (const int rc = masked_adam_plan(n, plan); rc != PLEAS_OK) return rc;
+    if (step < 1) return bad_arg("n < 0 or step < 1");
+    if (plan.blocks == 0) return PLEAS_OK;
     // scalars prepared in double exactly like torch.optim.Adam (_single_tensor_adam)
     const double bc1 = 1.0 - std::pow((double)b1, step);
     const double bc2 = 1.0 - std::pow((double)b2, step);
     const double step_size = (double)lr / bc1;
     const double bc2_sqrt = std::sqrt(bc2);
     ProfScope prof(kProfMaskedAdam, 0.0, 8.0 * n * sizeof(float), (hipStream_t)stream_);
-    hipLaunchKernelGGL(masked_adam_kernel, dim3(ew_grid(n)), dim3(kEwThreads), 0, (hipStream_t)stream_, p, g, mask, m, v,
+    hipLaunchKernelGGL(masked_adam_kernel, dim3(plan.blocks), dim3(kEwThreads), 0, (hipStream_t)stream_, p, g, mask, m, v,
                        n, (float)(1.0 - (double)b1), b2, (float)(1.0 - (double)b2), (float)step_size,
                        (float)bc2_sqrt, eps);
     PLEAS_LAUNCH_CHECK("masked_adam_kernel");
@@ -776,10 +898,11 @@ extern "C" size_t pleas_sqerr_ws_bytes(int64_t n) {
 extern "C" int pleas_sqerr(const float* a, const float* b, int64_t n, float scale, int accumulate, float* out,
                            float dscale, float* diff, void* ws, size_t ws_bytes, void* stream_) {
     if (!a || !b || !out) return bad_arg("null pointer");
-    if (n < 0) return bad_arg("n < 0");
+    StreamPlan p;
+    if (const int rc = sqerr_plan(n, p); rc != PLEAS_OK) return rc;
     if (!ws || ws_bytes < pleas_sqerr_ws_bytes(n)) return PLEAS_ENOMEM;
     hipStream_t stream = (hipStream_t)stream_;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, kEwThreads), kSqBlocks));
+    const int blocks = (int)p.blocks;
     ProfScope prof(kProfSqerr, 0.0, (diff ? 3.0 : 2.0) * n * sizeof(float), stream);
     hipLaunchKernelGGL(sqerr_partial_kernel, dim3(blocks), dim3(kEwThreads), 0, stream, a, b, n, dscale, diff,
                        (float*)ws);
@@ -831,23 +954,23 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const float* __restric
 
 extern "C" int pleas_channel_sum(const float* x, int N, int C, int64_t HW, float* out, void* stream_) {
     if (!x || !out) return bad_arg("channel_sum: null pointer");
-    if (N <= 0 || C <= 0 || HW <= 0) return bad_arg("channel_sum: empty tensor");
-    hipLaunchKernelGGL(channel_sum_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream_, x, N, C, (long long)HW, out);
+    StreamPlan p;
+    if (const int rc = channel_sum_plan(N, C, HW, all_aligned16(x), p); rc != PLEAS_OK) return rc;
+    hipLaunchKernelGGL(channel_sum_kernel, dim3(p.blocks), dim3(256), 0, (hipStream_t)stream_, x, N, C, (long long)HW, out);
     PLEAS_LAUNCH_CHECK("channel_sum_kernel");
     return PLEAS_OK;
 }
 
 extern "C" int pleas_pool_gather(const float* x, const int32_t* src, float* y, int64_t N, int C, int64_t HW, int K, void* stream_) {
     if (!x || !y) return bad_arg("pool_gather: null pointer");
-    if (N < 0 || C <= 0 || HW <= 0 || K <= 0) return bad_arg("pool_gather: empty tensor");
-    if (!src && K != C) return bad_arg("pool_gather: K != C without a channel map");
-    const int64_t rows = N * K;
-    if (rows == 0) return PLEAS_OK;
-    if (rows >= ((int64_t)1 << 40) || N * C >= ((int64_t)1 << 40)) return bad_arg("pool_gather: tensor too large");
+    StreamPlan p;
+    if (const int rc = pool_gather_plan(N, C, HW, K, src != nullptr, all_aligned16(x), p); rc != PLEAS_OK) return rc;
+    if (p.blocks == 0) return PLEAS_OK;
+    const int64_t rows = p.work;
     hipStream_t stream = (hipStream_t)stream_;
-    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(rows, kEwThreads / 64), (int64_t)1 << 20);
+    const unsigned grid = p.blocks;
     ProfScope prof(kProfBnAct, 0.0, ((double)rows * HW + (double)rows) * sizeof(float), stream);
-    if (HW % 4 == 0 && ((uintptr_t)x & 15) == 0)
+    if (p.vec == 4)
         hipLaunchKernelGGL((pool_gather_kernel<4>), dim3(grid), dim3(kEwThreads), 0, stream, x, src, y, rows, C, K, HW);
     else
         hipLaunchKernelGGL((pool_gather_kernel<1>), dim3(grid), dim3(kEwThreads), 0, stream, x, src, y, rows, C, K, HW);
@@ -858,10 +981,11 @@ extern "C" int pleas_pool_gather(const float* x, const int32_t* src, float* y, i
 extern "C" int pleas_top1_count(const float* logits, const int64_t* labels, int64_t N, int C, int64_t* hits, int64_t* pred,
                                 void* stream_) {
     if (!logits || !labels || !hits) return bad_arg("top1_count: null pointer");
-    if (N < 0 || C <= 0) return bad_arg("top1_count: empty rows");
-    if (N == 0) return PLEAS_OK;
+    StreamPlan p;
+    if (const int rc = top1_count_plan(N, C, p); rc != PLEAS_OK) return rc;
+    if (p.blocks == 0) return PLEAS_OK;
     if (((uintptr_t)hits & 7) != 0) return bad_arg("top1_count: hits must be 8-byte aligned");
-    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(N, kEwThreads / 64), kEwMaxBlocks);
+    const unsigned grid = p.blocks;
     hipLaunchKernelGGL(top1_count_kernel, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream_, logits, labels, N, C,
                        reinterpret_cast<unsigned long long*>(hits), pred);
     PLEAS_LAUNCH_CHECK("top1_count_kernel");

@@ -739,6 +739,29 @@ def sqerr(a: torch.Tensor, b: torch.Tensor, scale: float, out: torch.Tensor, acc
     return out
 
 
+STREAM_OPS = ("merge_blocks", "bn_act", "bn_act_maxpool", "masked_adam", "sqerr", "target_residual", "channel_sum",
+              "pool_gather", "top1_count", "bn_train_fold")      # PLEAS_STREAM_*, in order
+
+
+def stream_plan_info(op: str, *geo: int, aligned: bool = True) -> dict:
+    """The launch shape of a streaming kernel for a geometry (``pleas_stream_plan_info``; no GPU work, no tensors), computed by
+    the function the launch computes it with.  ``op``: a name of ``STREAM_OPS``; ``geo``: that kernel's sizes in the order
+    include/pleas_hip.h lists them; ``aligned``: whether every pointer of the launch's 16-byte predicate is 16-byte aligned.
+    Returns ``vec`` (floats per load, 4 / 1), ``form`` (bn_act_maxpool: "general" / "stem"), ``blocks``, ``threads``, ``sweeps`` of
+    the grid-stride loop (channel_sum / bn_train_fold: trips of a thread's loop over one slab) and, for bn_train_fold, ``S``."""
+    if op not in STREAM_OPS:
+        raise PleasHipError("stream_plan_info: unknown kernel %r" % (op,))
+    g = (ctypes.c_int64 * max(len(geo), 1))(*(int(v) for v in geo))
+    info = (ctypes.c_int * 6)()
+    check(_lib.lib().pleas_stream_plan_info(STREAM_OPS.index(op), g, len(geo), int(bool(aligned)), info), "pleas_stream_plan_info")
+    out = {"vec": info[0], "blocks": info[2], "threads": info[3], "sweeps": info[4]}
+    if op == "bn_act_maxpool":
+        out["form"] = ("general", "stem")[info[1]]
+    if op == "bn_train_fold":
+        out["S"] = info[5]
+    return out
+
+
 # ---------------------------------------------------------------------------------------- PLeaS layer fitting
 def target_residual(out: torch.Tensor, o1: torch.Tensor, o2: torch.Tensor, row1: torch.Tensor, row2: torch.Tensor,
                     n_merged: int, dscale: float, partials: torch.Tensor, resid: Optional[torch.Tensor] = None) -> int:
