@@ -712,6 +712,46 @@ int pleas_dw_wgrad_batch(const pleas_dw_wgrad_layer* layers, int n_layers, void*
                          void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Closed-form fit of depthwise layers (csrc/dw_normal_eq.hip): per-channel normal equations.  The objective of a depthwise layer
+ * separates per channel; each channel is a least-squares problem in K*K (+ 1 with a bias) unknowns.
+ * Per channel c and output pixel r = (n, oy, ox), v_r in R^D, D = K*K + 2:
+ *   v_r[ky*K + kx] = ip[n][c][oy*stride + ky - pad][ox*stride + kx - pad] (0 outside the image; the layer's tap order),
+ *   v_r[K*K] = 1,  v_r[K*K + 1] = tgt[n][c][oy][ox], the fp32 value pleas_merge_blocks stores for (o1, o2, row1, row2, n_merged):
+ *   coef * ([row1[c] >= 0] o1 + [row2[c] >= 0] o2), coef = 0.5 below n_merged, the sum rounded to fp32 once; never materialised.
+ * pleas_dw_normal_eq_accum: S[c] += sum_r v_r v_r^T for every listed layer, ONE grouped launch.  double S[C][D][D] row-major; only
+ *   the LOWER triangle with the diagonal is written, the strict upper triangle is left untouched.  The entries: G (taps x taps),
+ *   row K*K the column sums of U and the count M, row K*K + 1 h = sum u * t, sum t and sum t^2.  The bias column is always
+ *   accumulated.  Two entries of one launch may not share an S.
+ * Arithmetic: every fp32 x fp32 product exact in fp64 (v_mfma_f64_16x16x4_f64), every sum in fp64.
+ * Determinism: no atomics; per (channel, slab of 4096 output pixels) partial tiles, then the slabs in slab order from 0 and S +=
+ *   that sum; the split is a function of the geometry alone, grouped and alone give the same bits (header of the .hip file).
+ * Limits, alignment and errors are those of pleas_dw_fwd_batch: K odd in 1 .. 7, stride 1 or 2, pad <= K / 2, every per-call element
+ *   count below 2^30; ip, o1, o2 and S 16-byte aligned; EINVAL before anything is enqueued for an empty list, a NULL pointer, a
+ *   misaligned base, N <= 0, n_merged outside 0 .. C, a refused geometry; a NULL or short workspace: PLEAS_ENOMEM.
+ *   pleas_dw_normal_eq_ws_bytes is host only, reads no pointer of a layer, and returns 0 (message in pleas_last_error) for a list
+ *   the launch would refuse on its geometry.  ws / ws_fresh as in pleas_gram_batch.
+ * pleas_dw_normal_eq_solve: per channel, T = K*K + has_bias unknowns,  (G_T + ridge * mean(diag G_T) I) x = h_T  by fp64 Cholesky
+ *   (the rule of pleas_cholesky_solve_batched; with a bias the count M is on the diagonal); x is rounded once to fp32 into w[c][:]
+ *   (w [C][1][K][K]) and bias[c].  A pivot that is not positive sets status[c] = 1 and leaves that channel's w and bias untouched
+ *   (an all-zero channel without bias); otherwise status[c] = 0.  S, w, bias, status: DEVICE memory; one wave per channel.
+ * pleas_dw_normal_eq_solve_host: the same routine (csrc/dw_neq_solve.hpp) on HOST memory; `stream` is ignored. */
+typedef struct pleas_dw_neq_layer {
+    const float* ip;     /* [N][C][Hin][Win] merged input */
+    const float* o1;     /* [N][Csrc][Ho*Wo] source-layer outputs */
+    const float* o2;
+    const int32_t* row1; /* [C] block maps (DEVICE), -1 = absent */
+    const int32_t* row2;
+    double* S;           /* [C][D][D], accumulated in place */
+    int N, C, Hin, Win, K, stride, pad, Csrc, n_merged;
+} pleas_dw_neq_layer;
+size_t pleas_dw_normal_eq_ws_bytes(const pleas_dw_neq_layer* layers, int n_layers);
+int pleas_dw_normal_eq_accum(const pleas_dw_neq_layer* layers, int n_layers, void* ws, size_t ws_bytes, int ws_fresh, void* stream);
+int pleas_dw_normal_eq_solve(const double* S, int C, int K, int has_bias, double ridge, float* w, float* bias, int* status,
+                             void* stream);
+int pleas_dw_normal_eq_solve_host(const double* S, int C, int K, int has_bias, double ridge, float* w, float* bias, int* status,
+                                  void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The path's exchange step under data parallelism (no reference counterpart -- the reference is
  * single-GPU): buf[0..n) := sum over the ranks of `comm`, in place, ONE RCCL all-reduce (fp32, sum) enqueued on `stream`.
  * What is exchanged: the flat cost arena of activation matching (all group matrices back to back, ResNet-101: 41 MB) before

@@ -111,6 +111,11 @@ SIGNATURES = {
     "pleas_dw_fwd_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "pleas_dw_wgrad_batch_ws_bytes": (c_size_t, [c_void_p, c_int]),
     "pleas_dw_wgrad_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "pleas_dw_normal_eq_ws_bytes": (c_size_t, [c_void_p, c_int]),
+    "pleas_dw_normal_eq_accum": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "pleas_dw_normal_eq_solve": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pleas_dw_normal_eq_solve_host": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
     "pleas_gram_batch_ws_bytes": (c_size_t, [c_void_p, c_int, POINTER(c_int), c_int]),
     "pleas_gram_plan_info": (c_int, [c_int, c_int, c_int64, c_int, POINTER(c_int)]),
     "pleas_gram_batch_plan_info": (c_int, [c_void_p, c_int, POINTER(c_int), c_int, POINTER(c_int)]),
@@ -160,6 +165,13 @@ class DwWgradLayer(ctypes.Structure):
     """struct pleas_dw_wgrad_layer"""
     _fields_ = [("resid", c_void_p), ("ip", c_void_p), ("grad", c_void_p), ("N", c_int), ("C", c_int), ("Hin", c_int),
                 ("Win", c_int), ("K", c_int), ("stride", c_int), ("pad", c_int)]
+
+
+class DwNeqLayer(ctypes.Structure):
+    """struct pleas_dw_neq_layer"""
+    _fields_ = [("ip", c_void_p), ("o1", c_void_p), ("o2", c_void_p), ("row1", c_void_p), ("row2", c_void_p), ("S", c_void_p),
+                ("N", c_int), ("C", c_int), ("Hin", c_int), ("Win", c_int), ("K", c_int), ("stride", c_int), ("pad", c_int),
+                ("Csrc", c_int), ("n_merged", c_int)]
 
 
 class GramNode(ctypes.Structure):

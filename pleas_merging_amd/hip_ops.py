@@ -1077,6 +1077,104 @@ class DwWgradBatch(_GroupedLaunch):
         a.N, a.C, a.Hin, a.Win, a.K, a.stride, a.pad = geo
 
 
+# ---------------------------------------------------------------------------------------- depthwise closed form
+# What ``solver="normal_eq"`` does with a depthwise layer the Adam fitter takes on its own kernels (``plan.dw``):
+#   "refuse"  the fitter refuses the network, as every release so far (the default)
+#   "hip"     csrc/dw_normal_eq.hip: per-channel normal equations by ``DwNormalEqBatch``, solved by ``dw_normal_eq_solve``
+# ``PLEAS_DEPTHWISE_CLOSED_FORM`` in the environment sets the process's mode, ``depthwise_closed_form`` a block's.
+DEPTHWISE_CLOSED_FORMS = ("refuse", "hip")
+
+
+def _depthwise_closed_form_checked(mode) -> str:
+    if mode not in DEPTHWISE_CLOSED_FORMS:
+        raise ValueError("depthwise closed form %r is not one of %s" % (mode, DEPTHWISE_CLOSED_FORMS))
+    return mode
+
+
+DEPTHWISE_CLOSED_FORM = _depthwise_closed_form_checked(os.environ.get("PLEAS_DEPTHWISE_CLOSED_FORM", "refuse"))
+
+
+@contextlib.contextmanager
+def depthwise_closed_form(mode: str):
+    """``DEPTHWISE_CLOSED_FORM = mode`` for the block, the previous mode again afterwards (also when the block raises).
+    Process-wide, as ``depthwise_form``.  ``NormalEqFitter`` reads the mode when it is BUILT."""
+    global DEPTHWISE_CLOSED_FORM
+    before, DEPTHWISE_CLOSED_FORM = DEPTHWISE_CLOSED_FORM, _depthwise_closed_form_checked(mode)
+    try:
+        yield
+    finally:
+        DEPTHWISE_CLOSED_FORM = before
+
+
+class DwNormalEqBatch(_GroupedLaunch):
+    """Per-channel normal equations of the depthwise layers of one batch in ONE grouped launch (``pleas_dw_normal_eq_accum``):
+    ``S[c] += sum_r v_r v_r^T`` with ``v_r`` = (the K*K taps of ``ip`` under output pixel r, 1, the merged target of (o1, o2, row1,
+    row2, n_merged)); ``S`` fp64 [C, D, D], D = K*K + 2, lower triangle.  Two entries of one launch may not share an ``S``."""
+
+    STRUCT, WS_BYTES, LAUNCH = _lib.DwNeqLayer, "pleas_dw_normal_eq_ws_bytes", "pleas_dw_normal_eq_accum"
+
+    def add(self, ip, o1, o2, row1, row2, n_merged: int, S, stride: int = 1, pad: int = 0) -> None:
+        for t in (ip, o1, o2):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise PleasHipError("DwNormalEqBatch.add: contiguous fp32 tensors on the GPU expected")
+        if ip.dim() != 4 or not S.is_cuda or S.dtype != torch.float64 or not S.is_contiguous() or S.dim() != 3 or S.shape[0] != ip.shape[1] \
+                or S.shape[1] != S.shape[2]:
+            raise PleasHipError("DwNormalEqBatch.add: ip [N, C, H, W] and a contiguous fp64 S [C, D, D] on the GPU expected, got %s and %s"
+                                % (tuple(ip.shape), tuple(S.shape)))
+        N, C, Hin, Win = ip.shape
+        K = math.isqrt(max(0, int(S.shape[1]) - 2))
+        if K * K + 2 != S.shape[1]:
+            raise PleasHipError("DwNormalEqBatch.add: S must be [C, K*K + 2, K*K + 2], got %s" % (tuple(S.shape),))
+        want = (N, (Hin + 2 * pad - K) // stride + 1, (Win + 2 * pad - K) // stride + 1)
+        if o1.shape != o2.shape or o1.dim() != 4 or (o1.shape[0],) + tuple(o1.shape[2:]) != want:
+            raise PleasHipError("DwNormalEqBatch.add: o1 / o2 must be [N, Csrc, Ho, Wo] = [%d, Csrc, %d, %d]" % want)
+        for r in (row1, row2):
+            if not r.is_cuda or r.dtype != torch.int32 or r.numel() != C or not r.is_contiguous():
+                raise PleasHipError("DwNormalEqBatch.add: row maps must be contiguous int32 tensors of %d entries on the GPU" % C)
+        self._queue((ip, o1, o2, row1, row2, S), (N, C, Hin, Win, K, int(stride), int(pad), o1.shape[1], int(n_merged)))
+
+    def _fill(self, a, tensors, geo) -> None:
+        a.ip, a.o1, a.o2, a.row1, a.row2, a.S = (t.data_ptr() for t in tensors)
+        a.N, a.C, a.Hin, a.Win, a.K, a.stride, a.pad, a.Csrc, a.n_merged = geo
+
+
+def _dw_neq_solve_args(name: str, S: torch.Tensor, K: int, has_bias: bool, w: torch.Tensor, bias: Optional[torch.Tensor], cuda: bool):
+    K = int(K)
+    D = K * K + 2
+    if S.dtype != torch.float64 or S.dim() != 3 or tuple(S.shape[1:]) != (D, D) or not S.is_contiguous() or S.is_cuda != cuda:
+        raise PleasHipError("%s: a contiguous fp64 S [C, %d, %d] in %s memory expected, got %s"
+                            % (name, D, D, "device" if cuda else "host", tuple(S.shape)))
+    C = int(S.shape[0])
+    if w.dtype != torch.float32 or w.numel() != C * K * K or not w.is_contiguous() or w.device != S.device:
+        raise PleasHipError("%s: w must be a contiguous fp32 [C, 1, K, K] tensor beside S" % name)
+    if has_bias and (bias is None or bias.dtype != torch.float32 or bias.numel() != C or not bias.is_contiguous() or bias.device != S.device):
+        raise PleasHipError("%s: has_bias needs a contiguous fp32 bias of %d elements beside S" % (name, C))
+    status = torch.zeros(C, dtype=torch.int32, device=S.device)
+    return C, K, status
+
+
+def dw_normal_eq_solve(S: torch.Tensor, K: int, has_bias: bool, ridge: float, w: torch.Tensor,
+                       bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per channel ``(G_T + ridge * mean(diag G_T) I) x = h_T`` from ``S`` (``DwNormalEqBatch``) by fp64 Cholesky, ``x`` rounded once to
+    fp32 into ``w[c]`` (and ``bias[c]``) in place (``pleas_dw_normal_eq_solve``).  Returns the int32 status per channel: 1 = a pivot
+    was not positive, that channel's ``w`` and ``bias`` are untouched."""
+    C, K, status = _dw_neq_solve_args("dw_normal_eq_solve", S, K, has_bias, w, bias, True)
+    check(_lib.lib().pleas_dw_normal_eq_solve(S.data_ptr(), C, K, int(bool(has_bias)), float(ridge), w.data_ptr(),
+                                              bias.data_ptr() if has_bias else None, status.data_ptr(), _stream()),
+          "pleas_dw_normal_eq_solve")
+    return status
+
+
+def dw_normal_eq_solve_host(S: torch.Tensor, K: int, has_bias: bool, ridge: float, w: torch.Tensor,
+                            bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dw_normal_eq_solve`` on host tensors (``pleas_dw_normal_eq_solve_host``: the same routine, no GPU)."""
+    C, K, status = _dw_neq_solve_args("dw_normal_eq_solve_host", S, K, has_bias, w, bias, False)
+    check(_lib.lib().pleas_dw_normal_eq_solve_host(S.data_ptr(), C, K, int(bool(has_bias)), float(ridge), w.data_ptr(),
+                                                   bias.data_ptr() if has_bias else None, status.data_ptr(), None),
+          "pleas_dw_normal_eq_solve_host")
+    return status
+
+
 # ---------------------------------------------------------------------------------------- Linear
 # Which kernel an nn.Linear the library runs itself goes through (the probe's head, the inference graph's classifier):
 #   "conv"  ``pleas_conv2d_fwd`` with H = W = KH = KW = 1 on 4-D views, and ``channel_sum`` for the bias gradient: the calls and

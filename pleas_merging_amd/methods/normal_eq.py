@@ -15,6 +15,11 @@ flat fp32 arena, so a multi-GPU run shards whole batches over ranks and all-redu
 before the solve.  The K x K systems of all layers (and mask patterns) are solved by ONE batched call of
 the HIP blocked Cholesky (``pleas_cholesky_solve_batched``); a system whose fp32 factorisation hits a
 non-positive pivot is redone in fp64 on the vendor solver and counted in ``info["fp64_fallbacks"]``.
+
+Depthwise layers (``plan.dw``) under ``hip_ops.depthwise_closed_form("hip")``: the objective separates per channel, each channel a
+least-squares problem in K*K (+ 1) unknowns.  ONE grouped launch per half-batch accumulates the per-channel Gram matrices of all
+such layers in fp64 (``pleas_dw_normal_eq_accum`` into the flat arena ``S_flat``, the target never materialised), one
+``pleas_dw_normal_eq_solve`` per layer writes the weights.  They have no dense ``A`` / ``B^T``.
 """
 from __future__ import annotations
 
@@ -37,8 +42,9 @@ class NormalEqFitter(_LayerFitter):
     def __init__(self, *args, ridge: float = 1e-6, shard_solve: bool = True, **kwargs):
         super().__init__(*args, **kwargs)
         # the Adam-faithful fitter fits such layers on the vendor's operators -- depthwise ones on their own kernels under
-        # depthwise_form("hip") --; the closed form does neither
-        refused = [p.name for p in self.plans if p.name in self.vendor_layers or p.dw]
+        # depthwise_form("hip") --; the closed form takes the latter under depthwise_closed_form("hip") (read here, once)
+        self.dw_closed_form = self.ops.DEPTHWISE_CLOSED_FORM
+        refused = [p.name for p in self.plans if p.name in self.vendor_layers or (p.dw and self.dw_closed_form != "hip")]
         if refused:
             raise NotImplementedError("solver='normal_eq' takes dense, undilated Conv2d layers with a square kernel / stride / "
                                       "padding; not supported: %s (solver='adam' fits them)" % ", ".join(refused))
@@ -48,7 +54,8 @@ class NormalEqFitter(_LayerFitter):
         # repeated on every one (0.2 s of an 8-rank job's 1.6 s)
         self.shard_solve = bool(shard_solve)
         dev = self.device
-        self.K: List[int] = [int(math.prod(plan.w_shape[1:])) for plan in self.plans]
+        # a depthwise layer has no dense system: K = 0, empty views of the two arenas; its per-channel systems live in S_flat
+        self.K: List[int] = [0 if plan.dw else int(math.prod(plan.w_shape[1:])) for plan in self.plans]
         cout = [plan.w_shape[0] for plan in self.plans]
         self.A_flat = torch.zeros(sum(k * k for k in self.K), dtype=torch.float32, device=dev)
         self.B_flat = torch.zeros(sum(k * co for k, co in zip(self.K, cout)), dtype=torch.float32, device=dev)
@@ -59,8 +66,16 @@ class NormalEqFitter(_LayerFitter):
         # bias columns (Linear layers): column sums of U, of op, and the row count
         self.bias_stats: Dict[int, List[torch.Tensor]] = {
             i: [torch.zeros(self.K[i], device=dev), torch.zeros(p.w_shape[0], device=dev), torch.zeros(1, device=dev)]
-            for i, p in enumerate(self.plans) if p.b is not None}
+            for i, p in enumerate(self.plans) if p.b is not None and not p.dw}
         self.neq = self.ops.NormalEqBatch(dev)
+        # depthwise layers: fp64 S [C][D][D], D = K*K + 2, back to back in one arena (every layer on a 16-byte boundary)
+        self.dw_D: Dict[int, int] = {i: p.w_shape[2] * p.w_shape[3] + 2 for i, p in enumerate(self.plans) if p.dw}
+        sizes = [(self.plans[i].w_shape[0] * d * d + 1) // 2 * 2 for i, d in self.dw_D.items()]
+        self.S_flat = torch.zeros(sum(sizes), dtype=torch.float64, device=dev)
+        self.S: Dict[int, torch.Tensor] = {
+            i: s[:self.plans[i].w_shape[0] * d * d].view(self.plans[i].w_shape[0], d, d)
+            for (i, d), s in zip(self.dw_D.items(), self.S_flat.split(sizes))}
+        self.dw_neq = self.ops.DwNormalEqBatch(dev)
         self.sources._slice_batch = False   # data parallel here = whole batches per rank (train_normal_eq), never sample slices
 
     def _hip_geometry_ok(self, plan: _LayerPlan, ip: torch.Tensor) -> bool:
@@ -84,6 +99,10 @@ class NormalEqFitter(_LayerFitter):
                     continue
                 mod = plan.mod
                 in_maps, out_maps = plan.halves[h]
+                if plan.dw:    # the merged input joins the grouped merge; the target is formed inside the accumulate kernel
+                    ip = self.merge.add(in1[name], in2[name], 1, *in_maps)
+                    self.dw_neq.add(ip, out1[name], out2[name], *out_maps, self.S[idx], mod.stride[0], mod.padding[0])
+                    continue
                 grouped = self._hip_geometry_ok(plan, in1[name]) and plan.b is None
                 merge = self.merge.add if grouped else ops.merge_blocks     # grouped: filled by merge.flush() below
                 ip = merge(in1[name], in2[name], 1, *in_maps)
@@ -122,6 +141,7 @@ class NormalEqFitter(_LayerFitter):
             self.merge.flush()
             self.neq.flush()
             self.wgrad.flush()
+            self.dw_neq.flush()
         self._end_update()
 
     @torch.no_grad()
@@ -129,6 +149,8 @@ class NormalEqFitter(_LayerFitter):
         """Closed-form weights for every layer -> the parameter arena.  Returns per-layer info."""
         dp_sum_(self.A_flat, self.world)
         dp_sum_(self.B_flat, self.world)
+        if self.S_flat.numel():
+            dp_sum_(self.S_flat, self.world)
         for s in self.bias_stats.values():
             for t in s:
                 dp_sum_(t, self.world)
@@ -136,7 +158,7 @@ class NormalEqFitter(_LayerFitter):
         # arena, whichever rank contracted into it -- a rank whose share of the batches was empty has seen no geometry of its
         # own and takes the others' (the layers' image sizes; the batch size plays no part)
         mine = self.neq.seen()
-        geos = {i: mine[A.data_ptr()][1] for i, A in enumerate(self.A) if A.data_ptr() in mine}
+        geos = {i: mine[A.data_ptr()][1] for i, A in enumerate(self.A) if A.numel() and A.data_ptr() in mine}
         if self.world > 1 and dist.is_initialized():
             every = [None] * dist.get_world_size()
             dist.all_gather_object(every, geos)
@@ -146,8 +168,20 @@ class NormalEqFitter(_LayerFitter):
         self.neq.finalize([(self.A[i], g) for i, g in sorted(geos.items())])
         info: Dict[str, float] = {}
         jobs, finals = [], []   # (W, rows, free, A_FF, rhs, A_FF backup) per solve; (plan, W, layout) per layer
-        owner = solve_owners(self.K, [p.w_shape[0] for p in self.plans], self.world if self.shard_solve else 1)
+        dw_T = {i: d - 2 + (self.plans[i].b is not None) for i, d in self.dw_D.items()}       # unknowns per channel
+        owner = solve_owners(self.K, [p.w_shape[0] for p in self.plans], self.world if self.shard_solve else 1, dw_T)
+        dw_status = []
         for idx, plan in enumerate(self.plans):
+            if plan.dw:
+                info[plan.name] = float(dw_T[idx])
+                if owner[idx] != self.rank % max(1, self.world):
+                    continue
+                if not bool((self.mask[plan.off_w:plan.off_w + plan.w.numel()] > 0.5).all()):
+                    raise NotImplementedError("solver='normal_eq': the depthwise layer %s has frozen weights" % plan.name)
+                # every channel is one unmasked system: straight into the parameter arena
+                dw_status.append(self.ops.dw_normal_eq_solve(self.S[idx], plan.w_shape[2], plan.b is not None, self.ridge,
+                                                             plan.w, plan.b))
+                continue
             if owner[idx] != self.rank % max(1, self.world):
                 info[plan.name] = float(self.K[idx])
                 continue
@@ -195,6 +229,8 @@ class NormalEqFitter(_LayerFitter):
                 info["fp64_fallbacks"] = info.get("fp64_fallbacks", 0.0) + 1.0
                 sol = _spd_solve_fp64(A_orig, rhs0, self.ridge)
             W[rows[:, None], free[None, :]] = sol
+        if dw_status:
+            info["dw_singular_channels"] = float(sum(int((s != 0).sum()) for s in dw_status))
         for plan, W, from_kpos in finals:
             if plan.b is not None:
                 plan.b.copy_(W[:, -1])
@@ -220,12 +256,15 @@ def exchange_solved_(arena: torch.Tensor, layer_views: List[List[torch.Tensor]],
     dp_sum_(arena, world)
 
 
-def solve_owners(K: List[int], cout: List[int], world: int) -> List[int]:
-    """Which rank factorises which layer: longest-processing-time dealing on the solve's flops (K^3 / 3 + 2 Cout K^2), ties by
-    index -- a pure function of the layer list, so every rank computes the same table."""
+def solve_owners(K: List[int], cout: List[int], world: int, dw_T: Dict[int, int] = None) -> List[int]:
+    """Which rank factorises which layer: longest-processing-time dealing on the solve's flops (K^3 / 3 + 2 Cout K^2; a depthwise
+    layer, index -> unknowns per channel in ``dw_T``: Cout T^3 / 3), ties by index -- a pure function of the layer list, so every rank
+    computes the same table."""
     if world <= 1:
         return [0] * len(K)
     cost = [k ** 3 / 3.0 + 2.0 * co * k * k for k, co in zip(K, cout)]
+    for i, t in (dw_T or {}).items():
+        cost[i] = cout[i] * t ** 3 / 3.0
     load, owner = [0.0] * world, [0] * len(K)
     for idx in sorted(range(len(K)), key=lambda i: (-cost[i], i)):
         r = min(range(world), key=lambda j: (load[j], j))
