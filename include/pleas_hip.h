@@ -198,7 +198,7 @@ size_t pleas_merge_batch_ws_bytes(const pleas_merge_item* items, int n_items);
 int pleas_merge_batch(const pleas_merge_item* items, int n_items, void* ws, size_t ws_bytes, int ws_fresh, void* stream);
 
 /* ------------------------------------------------------------------------------------
- * Frozen-source forward: inference BatchNorm (+ residual add) (+ ReLU) in one pass.
+ * Frozen-source forward: inference BatchNorm (+ residual add) (+ ReLU / ReLU6) in one pass.
  *
  * Replaces: the BatchNorm2d -> (out += identity) -> ReLU module chain inside `model1(x); model2(x)`
  *   (pleas/methods/pleas_merging.py:267-268, models put in eval() at :352-353): three vendor
@@ -207,30 +207,43 @@ int pleas_merge_batch(const pleas_merge_item* items, int n_items, void* ws, size
  *
  * x, res (nullable), y: [n][channels][inner] contiguous fp32;  scale[c] = weight[c] / sqrt(var[c] + eps),
  * shift[c] = bias[c] - mean[c] * scale[c]  (DEVICE, prepared once by the caller).
- *   y = x * scale[c] + shift[c] (+ res);   relu != 0 applies torch.relu's rule: v < 0 -> 0, a NaN stays a NaN.   y must not alias x.
+ *   y = act(x * scale[c] + shift[c] (+ res));   y must not alias x.
+ *
+ * `relu` is an activation code, here and in every entry point below that has the parameter (pleas_bn_act_tracked,
+ * pleas_bn_act_tracked_batches, pleas_bn_act_maxpool, pleas_conv2d_bn_act_fwd, pleas_conv2d_act_fwd, pleas_dwconv2d_fwd):
+ *   PLEAS_ACT_NONE   the sum itself;
+ *   PLEAS_ACT_RELU   torch.relu's rule in these four passes: v < 0 -> 0, a NaN stays a NaN;
+ *   PLEAS_ACT_RELU6  F.relu6 / torch.clamp(v, 0, 6) for every fp32 input, the same in all seven entry points:
+ *                    v < 0 ? 0 : (v > 6 ? 6 : v) -- a NaN stays a NaN, +inf -> 6, -inf -> 0, no rounding;
+ *   any other value is taken as PLEAS_ACT_RELU (the parameter used to be a 0 / 1 flag).
+ * The code is a runtime operand of the same kernels: no kernel form, plan entry or workspace depends on it.
  */
+#define PLEAS_ACT_NONE 0
+#define PLEAS_ACT_RELU 1
+#define PLEAS_ACT_RELU6 2
 int pleas_bn_act(const float* x, const float* scale, const float* shift, const float* res, float* y, int64_t n,
                  int channels, int64_t inner, int relu, void* stream);
 /* Same pass with the intermediate values kept, for activation matching (activation_matching.py:49-100 measures EVERY
- * node of the chain): y_bn = x * scale + shift and y_sum = y_bn + res are written when non-NULL, y is the final value. */
+ * node of the chain): y_bn = x * scale + shift and y_sum = y_bn + res are written when non-NULL, y is the final value under
+ * activation code `relu` (PLEAS_ACT_*); y_bn and y_sum do not depend on the code. */
 int pleas_bn_act_tracked(const float* x, const float* scale, const float* shift, const float* res, float* y_bn,
                          float* y_sum, float* y, int64_t n, int channels, int64_t inner, int relu, void* stream);
 
 /* The tracked pass on a tensor that holds `batches` batches back to back along n, each with its OWN affine map: scale /
  * shift are [batches][channels] (pleas_bn_train_fold_batches).  Replaces the same module chains when the twin forward of
  * activation_matching.py:49-100 carries several matching batches and the models are in train mode (batch statistics are
- * per batch: run_domainnet.py:172-186 never calls .eval()). */
+ * per batch: run_domainnet.py:172-186 never calls .eval()).  `relu`: a PLEAS_ACT_* code. */
 int pleas_bn_act_tracked_batches(const float* x, const float* scale, const float* shift, const float* res, float* y_bn,
                                  float* y_sum, float* y, int64_t n_per_batch, int batches, int channels, int64_t inner,
                                  int relu, void* stream);
 
-/* The same map followed by a max pooling window, one pass (a ResNet's stem: bn1 -> relu -> maxpool).
+/* The same map followed by a max pooling window, one pass (a ResNet's stem: bn1 -> relu -> maxpool); `relu`: a PLEAS_ACT_* code.
  *
  * Replaces: BatchNorm2d -> ReLU -> nn.MaxPool2d(kernel, stride, padding) of a frozen source forward
  *   (pleas/methods/pleas_merging.py:267-268 runs the whole model; only Conv2d / Linear inputs and outputs are hooked,
  *   :197-243, so the full-resolution activation between ReLU and the pooling is consumed by nothing and is not written).
  *   y[n][c][oh][ow] = max over the KH x KW window at (oh * stride - pad, ow * stride - pad) of act(x * scale[c] + shift[c]);
- *   out-of-range taps never win (torch pads with -inf), a NaN tap does, with or without relu; floor-mode output size, dilation 1.
+ *   out-of-range taps never win (torch pads with -inf), a NaN tap does, under every activation code; floor-mode output size, dilation 1.
  *   scale == NULL: plain max pooling of x.  y: [n][channels][Ho][Wo], must not alias x. */
 int pleas_bn_act_maxpool(const float* x, const float* scale, const float* shift, float* y, int64_t n, int channels, int H,
                          int W, int KH, int KW, int stride, int pad, int relu, void* stream);
@@ -587,7 +600,9 @@ int pleas_conv2d_fwd(const float* x, const float* w, const float* bias, float* y
  * source (torchvision Bottleneck: conv -> bn -> relu, conv3 -> bn3 -> (+ identity) -> relu, downsample conv -> bn) in its
  * epilogue:  y = conv(x, w) (+ bias)  is stored for the hooks of pleas_merging.py:197-231 (the layer's OUTPUT is a regression
  * target), and  z = act(y * scale[c] + shift[c] (+ res))  -- bit for bit what pleas_bn_act makes of y -- is stored beside it
- * from the registers, so y is not read back.  res (or NULL) and z are shaped like y; y, z, res 16-byte aligned. */
+ * from the registers, so y is not read back.  res (or NULL) and z are shaped like y; y, z, res 16-byte aligned.
+ * `relu`: a PLEAS_ACT_* code.  The stored y does not depend on it.  Under PLEAS_ACT_RELU6 z is bit for bit pleas_bn_act's, a NaN
+ * included; the ReLU arm of this epilogue is fmaxf(v, 0), which turns a NaN into 0 where pleas_bn_act keeps it. */
 int pleas_conv2d_bn_act_fwd(const float* x, const float* w, const float* bias, float* y, const float* scale,
                             const float* shift, const float* res, float* z, int relu, int N, int Cin, int Hin, int Win,
                             int Cout, int KH, int KW, int stride, int pad, int flags, void* stream);
@@ -598,7 +613,8 @@ int pleas_conv2d_bn_act_fwd(const float* x, const float* w, const float* bias, f
  * Replaces: the Conv2d -> BatchNorm2d -> (+ identity) -> ReLU module chains of `model(x)` in the evaluation helpers
  *   (pleas/methods/pleas_merging.py:469-496 eval_perm_model, :575-586 eval_whole_model, :499-570 the linear probe's frozen
  *   backbone), where no hook reads the convolution's output.
- * Same argument checks, alignment rules (x, w, z, res 16-byte aligned) and per-call size limits as its sibling. */
+ * Same argument checks, alignment rules (x, w, z, res 16-byte aligned), per-call size limits and activation codes (`relu`) as
+ * its sibling. */
 int pleas_conv2d_act_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
                          const float* res, float* z, int relu, int N, int Cin, int Hin, int Win, int Cout, int KH, int KW,
                          int stride, int pad, int flags, void* stream);
@@ -682,7 +698,9 @@ int pleas_wgrad_plan_info(const pleas_wgrad_layer* layers, int n_layers, int* in
  *   pad > K / 2; a misaligned base pointer; an element count at or above 2^30; grouped: an empty list, a NULL pointer of a layer
  *   (bias excepted), N <= 0, n_merged outside 0 .. C.  N == 0 (pleas_dwconv2d_fwd): PLEAS_OK, nothing is enqueued.  A workspace
  *   that is NULL or smaller than the *_ws_bytes answer: PLEAS_ENOMEM.  *_ws_bytes returns 0 (message in pleas_last_error) for a
- *   list the launch would refuse on its geometry; it reads no pointer of a layer.  ws / ws_fresh as in pleas_gram_batch. */
+ *   list the launch would refuse on its geometry; it reads no pointer of a layer.  ws / ws_fresh as in pleas_gram_batch.
+ * pleas_dwconv2d_fwd's `relu` is a PLEAS_ACT_* code: z = act(fma(y, scale[c], shift[c]) (+ res)); PLEAS_ACT_RELU6 gives pleas_bn_act's
+ *   bits, a NaN included; the ReLU arm is fmaxf(v, 0) as in the dense epilogue.  y does not depend on the code. */
 int pleas_dwconv2d_fwd(const float* x, const float* w, const float* bias, float* y, const float* scale, const float* shift,
                        const float* res, float* z, int relu, int N, int C, int Hin, int Win, int K, int stride, int pad,
                        void* stream);

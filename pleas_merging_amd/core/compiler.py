@@ -81,7 +81,7 @@ def _batchnorm2d(mod, ins, out):
     return links
 
 
-@_rule(_MODULE_RULES, nn.ReLU, nn.GELU, nn.Identity, nn.Dropout, nn.Sigmoid, nn.SiLU, nn.Tanh, nn.Hardswish)
+@_rule(_MODULE_RULES, nn.ReLU, nn.ReLU6, nn.Hardtanh, nn.GELU, nn.Identity, nn.Dropout, nn.Sigmoid, nn.SiLU, nn.Tanh, nn.Hardswish)
 def _elementwise_module(mod, ins, out):
     assert tuple(ins[0]) == tuple(out)
     return _same_axes(len(out))
@@ -161,7 +161,7 @@ def _flatten_fn(ins, out, args, kwargs):
     return _flatten_links(ins[0], start, end)
 
 
-@_rule(_FUNCTION_RULES, F.relu, F.gelu, torch.relu, torch.sigmoid, torch.sqrt, torch.tanh, F.silu, F.dropout)
+@_rule(_FUNCTION_RULES, F.relu, F.relu6, F.hardtanh, F.hardtanh_, F.gelu, torch.relu, torch.sigmoid, torch.sqrt, torch.tanh, F.silu, F.dropout)
 def _elementwise_fn(ins, out, args, kwargs):
     assert tuple(ins[0]) == tuple(out)
     return _same_axes(len(out))

@@ -41,6 +41,10 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // every table of a plan starts on a 256-byte boundary of the caller's workspace
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
+// PLEAS_ACT_RELU6 of every epilogue that carries an activation code: F.relu6 / torch.clamp(v, 0, 6) for every fp32 input -- both
+// comparisons are false for a NaN, which stays; +inf -> 6, -inf -> 0.  No rounding: the result is 0, 6 or v itself.
+__device__ __forceinline__ float relu6_keep_nan(float v) { return v < 0.f ? 0.f : (v > 6.f ? 6.f : v); }
+
 // Pointers that reach a kernel through a device-side table are "generic" to hipcc, which then emits
 // flat_load / flat_store: those count on lgkmcnt as well as vmcnt, so every LDS wait in the MFMA loop
 // also waits for the global prefetch.  Casting to the global address space gives global_load / global_store.

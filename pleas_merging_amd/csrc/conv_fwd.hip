@@ -71,7 +71,7 @@ struct FwdLayerDev {
                           // bit3: flat-shift tile (fwd_flat_tile), bits 4-5: its KIND
     int part_base;        // first loss-partial slot of this layer
     // the image modes: z = act(y * bn_scale[co] + bn_shift[co] (+ bn_res)) to `bn_z`
-    int bn_relu;             // ReLU after the affine map (+ identity)
+    int bn_relu;             // activation after the affine map (+ identity): a PLEAS_ACT_* code
     const float* bn_scale;   // [Cout]
     const float* bn_shift;   // [Cout]
     const float* bn_res;     // [N][Cout][HWo] or null
@@ -148,6 +148,16 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
     constexpr int SPR = kThreads / TM;       // threads per row of the statistics pass
     float st_bias = 0.f;
     if constexpr (fwd_has_stats(MODE)) st_bias = L.bias ? PLEAS_GLOBAL(L.bias)[min(i0 + tid / SPR, L.Cout - 1)] : 0.f;
+    // The image's activation (bn_relu is 0, 1 or 2: fwd_describe).  The ReLU arm is the select it always was; ReLU6 is two more
+    // selects against launch-uniform bounds that the other codes never reach (-inf / +inf), so every arm is straight-line code: a
+    // branch around a clamp of its own costs the unrolled pass registers (an occupancy step on the 128-row forms).  Both
+    // comparisons are false for a NaN: it stays, as in relu6_keep_nan -- whose values these are.
+    const bool relu1 = fwd_has_image(MODE) && L.bn_relu == PLEAS_ACT_RELU, relu6 = fwd_has_image(MODE) && L.bn_relu == PLEAS_ACT_RELU6;
+    const float act_lo = relu6 ? 0.f : -__builtin_inff(), act_hi = relu6 ? 6.f : __builtin_inff();
+    auto act6 = [&](const float v) {
+        const float f = v < act_lo ? 0.f : v;
+        return f > act_hi ? 6.f : f;
+    };
     const bool vec_ok = (L.HWo % 4 == 0);   // then a 4-pixel group never straddles samples and is 16-B aligned
     const int pg = (tid & 31) * 4;           // pixel group of this thread
     const uint32_t Pg = p0 + pg;
@@ -206,7 +216,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                     for (int e = 0; e < 4; ++e) {
                         y[e] = o[e] + ops.bias[j];
                         const float sm = fmaf(y[e], ops.scale[j], ops.shift[j]) + ta[bt][u][e];
-                        z[e] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
+                        z[e] = act6(relu1 ? fmaxf(sm, 0.f) : sm);
                     }
                     if (live) {
                         if constexpr (fwd_stores_y(MODE)) *(__attribute__((address_space(1))) f32x4*)(rb_ + (rbase + (uint32_t)(8 * j) * hw4)) = y;
@@ -254,7 +264,7 @@ __device__ __forceinline__ void fwd_epilogue(const FwdLayerDev& L, const FwdItem
                     const float y = o[e] + ops.bias[j];
                     const float sm = fmaf(y, ops.scale[j], ops.shift[j]) + (L.bn_res ? PLEAS_GLOBAL(L.bn_res)[at] : 0.f);
                     if constexpr (fwd_stores_y(MODE)) PLEAS_GLOBAL_W(L.resid)[at] = y;
-                    PLEAS_GLOBAL_W(L.bn_z)[at] = L.bn_relu ? fmaxf(sm, 0.f) : sm;
+                    PLEAS_GLOBAL_W(L.bn_z)[at] = act6(relu1 ? fmaxf(sm, 0.f) : sm);
                 } else {
                     float a = 0.f, b = 0.f;
                     if (ops.row1[j] >= 0) a = PLEAS_GLOBAL(L.o1)[((size_t)n * L.Csrc + ops.row1[j]) * L.HWo + p];
@@ -1254,7 +1264,7 @@ struct Conv2dCall {
     void* stream;
     const float *scale = nullptr, *shift = nullptr, *res = nullptr;      // the image modes: res may be null
     float* z = nullptr;
-    int relu = 0;                                // ReLU after the map
+    int relu = 0;                                // activation after the map: a PLEAS_ACT_* code (other values: ReLU)
 };
 // its description; ConvStats: the caller sets d.st_part / d.st_pb once its own refusals are past
 struct Conv2dPlan { FwdLayerDev d; size_t lds = 0; int TM = 128; };
@@ -1274,7 +1284,7 @@ static int conv2d_describe(const Conv2dCall& c, Conv2dPlan& p) {
     if (const int rc = fwd_describe(l, d, p.lds, p.TM); rc != PLEAS_OK) return rc;
     // no block maps: every source row is absent (fwd_load_maps), the masked gathers read the first floats of x
     d.ip = c.x; d.w = c.w; d.bias = c.bias; d.o1 = c.x; d.o2 = c.x; d.resid = c.y;
-    d.bn_scale = c.scale; d.bn_shift = c.shift; d.bn_res = c.res; d.bn_z = c.z; d.bn_relu = c.relu ? 1 : 0;
+    d.bn_scale = c.scale; d.bn_shift = c.shift; d.bn_res = c.res; d.bn_z = c.z; d.bn_relu = c.relu == PLEAS_ACT_RELU6 ? PLEAS_ACT_RELU6 : (c.relu ? PLEAS_ACT_RELU : PLEAS_ACT_NONE);
     return PLEAS_OK;
 }
 

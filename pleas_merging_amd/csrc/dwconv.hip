@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kDwThreads) void dw_fwd_kernel(const DwFwdArgs a) {
         if (a.z) {
             const float bn = a.scale ? fmaf(y, sc, sh) : y;
             const float sm = bn + (a.res ? a.res[at] : 0.f);
-            a.z[at] = a.relu ? fmaxf(sm, 0.f) : sm;
+            a.z[at] = a.relu == PLEAS_ACT_RELU6 ? relu6_keep_nan(sm) : a.relu ? fmaxf(sm, 0.f) : sm;
         }
     }
 }

@@ -118,6 +118,11 @@ __global__ __launch_bounds__(kEwThreads) void merge_blocks_kernel(
 
 // torch.relu's rule: a NaN stays a NaN (fmaxf(v, 0) would turn it into 0 and a diverged model would be evaluated on zeros)
 __device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+// The activation codes of include/pleas_hip.h: 0 none, 2 ReLU6 (F.relu6's rule: a NaN stays a NaN, +inf -> 6, -inf -> 0), every other
+// value ReLU.  `act` is kernel-uniform.
+__device__ __forceinline__ float act_keep_nan(float v, int act) {
+    return act == PLEAS_ACT_RELU6 ? relu6_keep_nan(v) : act ? relu_keep_nan(v) : v;
+}
 
 // ------------------------------------------------------------------------------------------
 // Inference BatchNorm folded to one affine map per channel, optional residual add, optional ReLU:
@@ -151,7 +156,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_kernel(const float* __restr
             for (int e = 0; e < 4; ++e) {
                 bn[e] = fmaf(q[e], a, b);
                 sm[e] = bn[e] + r[e];
-                o[e] = relu ? relu_keep_nan(sm[e]) : sm[e];
+                o[e] = act_keep_nan(sm[e], relu);
             }
             if (y_bn) reinterpret_cast<f32x4*>(y_bn)[idx] = bn;
             if (y_sum) reinterpret_cast<f32x4*>(y_sum)[idx] = sm;
@@ -161,7 +166,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_kernel(const float* __restr
             const float sm = bn + (res ? res[idx] : 0.f);
             if (y_bn) y_bn[idx] = bn;
             if (y_sum) y_sum[idx] = sm;
-            y[idx] = relu ? relu_keep_nan(sm) : sm;
+            y[idx] = act_keep_nan(sm, relu);
         }
     }
 }
@@ -198,7 +203,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_pool_kernel(const float* __
                 if (iw < 0 || iw >= W) continue;
                 float v = src[ih * W + iw];
                 if (scale) v = fmaf(v, a, b);
-                if (relu) v = relu_keep_nan(v);
+                v = act_keep_nan(v, relu);
                 if (v > best || v != v) best = v;
             }
         }
@@ -824,7 +829,7 @@ __global__ __launch_bounds__(kEwThreads) void bn_act_pool3s2_kernel(const float*
 #pragma unroll
             for (int e = 0; e < 9; ++e) {
                 if (scale) v[e] = fmaf(v[e], a, b);
-                if (relu) v[e] = relu_keep_nan(v[e]);
+                v[e] = act_keep_nan(v[e], relu);
             }
             if (q == 0) v[0] = ninf;       // the padding column never wins
 #pragma unroll

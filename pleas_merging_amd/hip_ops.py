@@ -487,6 +487,18 @@ def host_solve_minimax_assignment(A: torch.Tensor, maximize: bool = True) -> tor
 
 
 # ---------------------------------------------------------------------------------------- bn + add + relu
+# Activation codes of the fused epilogues (PLEAS_ACT_* of include/pleas_hip.h): the ``relu`` argument of every wrapper below.
+ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
+
+
+def _act_code(name: str, relu) -> int:
+    """The activation code of a wrapper's ``relu`` argument: ``False`` / ``True`` as ever (none / ReLU), or one of ``ACT_NONE``,
+    ``ACT_RELU``, ``ACT_RELU6``.  Anything else is refused here, before the library is reached."""
+    if isinstance(relu, (bool, int)) and int(relu) in (ACT_NONE, ACT_RELU, ACT_RELU6):
+        return int(relu)
+    raise PleasHipError("%s: activation %r is not False, True, ACT_NONE (0), ACT_RELU (1) or ACT_RELU6 (2)" % (name, relu))
+
+
 def _bn_act_args(name: str, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor]):
     """Checks shared by ``bn_act`` and ``bn_act_tracked``: returns ``(x, res, C, batches)``, x and res contiguous.  scale / shift
     ``[batches][C]``: x holds that many batches back to back along dim 0, each with its own affine map."""
@@ -510,17 +522,18 @@ def _bn_act_args(name: str, x: torch.Tensor, scale: torch.Tensor, shift: torch.T
 def bn_act(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor] = None,
            relu: bool = True) -> torch.Tensor:
     """``act(x * scale[c] + shift[c] (+ res))`` over dim 1 of a contiguous fp32 tensor: inference BatchNorm,
-    residual add and ReLU of a frozen source model in one pass (``pleas_bn_act``)."""
+    residual add and activation (``relu``: a bool or an ``ACT_*`` code) of a frozen source model in one pass (``pleas_bn_act``)."""
+    relu = _act_code("bn_act", relu)
     x, res, C, batches = _bn_act_args("bn_act", x, scale, shift, res)
     y = torch.empty_like(x)
     ptr = res.data_ptr() if res is not None else None
     if batches == 1:
         check(_lib.lib().pleas_bn_act(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), ptr, y.data_ptr(), x.shape[0], C,
-                                      math.prod(x.shape[2:]), int(relu), _stream()), "pleas_bn_act")
+                                      math.prod(x.shape[2:]), relu, _stream()), "pleas_bn_act")
     else:      # the tracked pass without its optional outputs is this pass
         check(_lib.lib().pleas_bn_act_tracked_batches(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), ptr, None, None,
                                                       y.data_ptr(), x.shape[0] // batches, batches, C,
-                                                      math.prod(x.shape[2:]), int(relu), _stream()),
+                                                      math.prod(x.shape[2:]), relu, _stream()),
               "pleas_bn_act_tracked_batches")
     return y
 
@@ -528,7 +541,8 @@ def bn_act(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optio
 def bn_act_maxpool(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], kernel: Tuple[int, int],
                    stride: int, padding: int, relu: bool = True) -> torch.Tensor:
     """``max_pool2d(act(x * scale[c] + shift[c]), kernel, stride, padding)`` of a contiguous fp32 NCHW tensor in one pass
-    (``pleas_bn_act_maxpool``); ``scale is None``: plain max pooling."""
+    (``pleas_bn_act_maxpool``); ``scale is None``: plain max pooling.  ``relu``: a bool or an ``ACT_*`` code."""
+    relu = _act_code("bn_act_maxpool", relu)
     _need_gpu(x) if scale is None else _need_gpu(x, scale, shift)
     if x.dim() != 4 or x.dtype != torch.float32:
         raise PleasHipError("bn_act_maxpool needs an fp32 [N, C, H, W] tensor")
@@ -543,7 +557,7 @@ def bn_act_maxpool(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Option
     y = torch.empty((N, C, max(Ho, 0), max(Wo, 0)), dtype=torch.float32, device=x.device)
     rc = _lib.lib().pleas_bn_act_maxpool(x.data_ptr(), scale.data_ptr() if scale is not None else None,
                                          shift.data_ptr() if scale is not None else None, y.data_ptr(), N, C, H, W, KH, KW,
-                                         stride, padding, int(relu), _stream())
+                                         stride, padding, relu, _stream())
     check(rc, "pleas_bn_act_maxpool")
     return y
 
@@ -551,9 +565,11 @@ def bn_act_maxpool(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Option
 def bn_act_tracked(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor], relu: bool,
                    keep_bn: bool = True):
     """One pass, every node of the chain kept: returns ``(bn, sum, act)`` = ``(x * scale + shift, bn + res, relu(sum))``;
-    ``sum`` is None without a residual and ``act`` is None without ``relu`` (``pleas_bn_act_tracked``).
+    ``sum`` is None without a residual and ``act`` is None without ``relu`` (``pleas_bn_act_tracked``).  ``relu``: a bool or an
+    ``ACT_*`` code; under ``ACT_RELU6`` ``act`` is ``F.relu6(sum)``.
     ``keep_bn=False``: the BatchNorm value itself is not needed by the caller (its matching cost is derived from the
     convolution node, ``GramBatch.add_derived``) and is not written unless it is the chain's last value."""
+    relu = _act_code("bn_act_tracked", relu)
     x, res, C, batches = _bn_act_args("bn_act_tracked", x, scale, shift, res)
     # the last value of the chain goes to `y`; earlier ones to the optional outputs
     y_bn = torch.empty_like(x) if ((res is not None or relu) and keep_bn) else None
@@ -563,7 +579,7 @@ def bn_act_tracked(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, re
                                                  res.data_ptr() if res is not None else None,
                                                  y_bn.data_ptr() if y_bn is not None else None,
                                                  y_sum.data_ptr() if y_sum is not None else None, y.data_ptr(),
-                                                 x.shape[0] // batches, batches, C, math.prod(x.shape[2:]), int(relu), _stream())
+                                                 x.shape[0] // batches, batches, C, math.prod(x.shape[2:]), relu, _stream())
     check(rc, "pleas_bn_act_tracked_batches")
     if res is None:
         return (y_bn, None, y) if relu else (y, None, None)
@@ -972,8 +988,10 @@ def dwconv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], str
 
     Without ``scale`` / ``act_out``: returns ``y`` (into ``out`` when given).  With ``scale`` and ``shift`` (fp32 [C]): also
     ``z = act(fma(y, scale, shift) (+ res))``, bit for bit ``bn_act(y, scale, shift, res, relu)``, and returns ``(y, z)``; with
-    ``out=False`` ``y`` is not stored and ``z`` alone is returned (``act_out``: the tensor ``z`` goes to)."""
+    ``out=False`` ``y`` is not stored and ``z`` alone is returned (``act_out``: the tensor ``z`` goes to).  ``relu``: a bool or an
+    ``ACT_*`` code."""
     name = "dwconv2d"
+    relu = _act_code(name, relu)
     _need_gpu(x, w)
     if x.dim() != 4 or not x.is_contiguous() or x.data_ptr() % 16:
         raise PleasHipError("%s: a contiguous, 16-byte aligned [N, C, H, W] input expected, got %s" % (name, tuple(x.shape)))
@@ -1006,7 +1024,7 @@ def dwconv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], str
         z = act_out if act_out is not None else torch.empty(shape, dtype=torch.float32, device=dev)
         _dw_image(name, "act_out", z, shape, dev)
     check(_lib.lib().pleas_dwconv2d_fwd(x.data_ptr(), w.data_ptr(), ptrs[0], y.data_ptr() if y is not None else None, ptrs[1], ptrs[2],
-                                        ptrs[3], z.data_ptr() if z is not None else None, int(bool(relu)), N, C, H, W, K, stride, pad,
+                                        ptrs[3], z.data_ptr() if z is not None else None, relu, N, C, H, W, K, stride, pad,
                                         _stream()), "pleas_dwconv2d_fwd")
     if not image:
         return y
@@ -1632,12 +1650,14 @@ def image_resample_chain(src_u8: torch.Tensor, plan_dev: torch.Tensor, plan: tor
 def conv2d_bn_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int, kpos_major: bool,
                   scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor], relu: bool):
     """``y = conv2d(x, w, bias)`` and ``z = bn_act(y, scale, shift, res, relu)`` from ONE launch (``pleas_conv2d_bn_act_fwd``):
-    the activated image is written from the registers that hold y, bit for bit what ``bn_act`` makes of y.  Returns ``(y, z)``."""
+    the activated image is written from the registers that hold y, bit for bit what ``bn_act`` makes of y.  Returns ``(y, z)``.
+    ``relu``: a bool or an ``ACT_*`` code."""
+    relu = _act_code("conv2d_bn_act", relu)
     operands, geometry, out_shape = _conv_call("conv2d_bn_act", x, w, bias, stride, pad, kpos_major, scale, shift)
     image = _image_operands("conv2d_bn_act", x, scale, shift, res, out_shape)
     y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
     z = torch.empty_like(y)
-    check(_lib.lib().pleas_conv2d_bn_act_fwd(*operands, y.data_ptr(), *image, z.data_ptr(), 1 if relu else 0, *geometry, _stream()),
+    check(_lib.lib().pleas_conv2d_bn_act_fwd(*operands, y.data_ptr(), *image, z.data_ptr(), relu, *geometry, _stream()),
           "pleas_conv2d_bn_act_fwd")
     return y, z
 
@@ -1674,7 +1694,8 @@ def conv2d_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], s
     """``z = bn_act(conv2d(x, w, bias), scale, shift, res, relu)`` with z as the ONLY output (``pleas_conv2d_act_fwd``): bit for
     bit the ``z`` of ``conv2d_bn_act``, the convolution's own output is never written.  For forwards nobody hooks (evaluation).
     A batch whose output crosses the per-call limit of the kernels is split along the sample axis (``conv2d_sample_split``)
-    into calls that write one ``z``.  ``_limit``: the output-element limit, for tests."""
+    into calls that write one ``z``.  ``_limit``: the output-element limit, for tests.  ``relu``: a bool or an ``ACT_*`` code."""
+    relu = _act_code("conv2d_act", relu)
     (_, wp, bp), geometry, out_shape = _conv_call("conv2d_act", x, w, bias, stride, pad, kpos_major, scale, shift)
     sp, tp, _ = _image_operands("conv2d_act", x, scale, shift, res, out_shape)
     (N, Cin, H, W), (_, Cout, Ho, Wo) = geometry[:4], out_shape
@@ -1691,7 +1712,7 @@ def conv2d_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], s
     fn, st = _lib.lib().pleas_conv2d_act_fwd, _stream()
     for at, n in parts:
         check(fn(x[at:at + n].data_ptr(), wp, bp, sp, tp, res[at:at + n].data_ptr() if res is not None else None,
-                 z[at:at + n].data_ptr(), 1 if relu else 0, n, *geometry[1:], st), "pleas_conv2d_act_fwd")
+                 z[at:at + n].data_ptr(), relu, n, *geometry[1:], st), "pleas_conv2d_act_fwd")
     return z
 
 

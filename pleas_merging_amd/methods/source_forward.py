@@ -1,4 +1,4 @@
-"""Frozen source forwards with BatchNorm / residual add / ReLU folded into one HIP pass.
+"""Frozen source forwards with BatchNorm / residual add / ReLU or ReLU6 folded into one HIP pass.
 
 The PLeaS loop runs ``model1(x); model2(x)`` under forward hooks on every Conv2d / Linear
 (reference pleas/methods/pleas_merging.py:267-268; both models in ``eval()``, :352-353).  Only the
@@ -10,6 +10,7 @@ be fused.  ``fuse_bn_act`` rewrites an fx trace of the model:
     bn(x)                              =>  bn_act(x, scale, shift, None, relu=False)
     bn(x) -> relu -> MaxPool2d         =>  bn_act_maxpool(x, scale, shift, kernel, stride, padding, relu=True)
                                            (the stem: the full-resolution ReLU output is never written)
+    ... -> relu6 in place of relu          =>  the same calls with ``relu=hip_ops.ACT_RELU6`` (``_is_relu`` lists the spellings)
 
     (train mode, ``train_convs=True``)
     HipConv(conv)(x) -> bn_train_fold  =>  HipConvBnStats: ONE call that stores the convolution's output and folds its batch statistics,
@@ -351,14 +352,49 @@ def _pool_window(node: torch.fx.Node, mods):
     return kernel, stride[0], padding[0]
 
 
-def _is_relu(node: torch.fx.Node, mods) -> bool:
+def _hardtanh_bounds(node: torch.fx.Node):
+    """``(min_val, max_val)`` of an ``F.hardtanh`` / ``F.hardtanh_`` call as the graph states them (defaults -1, 1); anything
+    that is not a constant stays what it is and equals no number."""
+    rest = tuple(node.args[1:])
+    return (rest[0] if rest else node.kwargs.get("min_val", -1.0), rest[1] if len(rest) > 1 else node.kwargs.get("max_val", 1.0))
+
+
+def _is_const(v, want: float) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and v == want
+
+
+def _is_relu(node: torch.fx.Node, mods) -> int:
+    """Which activation of the fused epilogues ``node`` is, in place or not: ``hip_ops.ACT_RELU`` (``nn.ReLU``, ``F.relu``,
+    ``torch.relu``, ``torch.relu_``, ``.relu()``, ``.relu_()``), ``hip_ops.ACT_RELU6`` (``nn.ReLU6``, ``nn.Hardtanh`` with bounds
+    (0, 6), ``F.relu6``, ``F.hardtanh`` / ``F.hardtanh_`` with constant bounds 0 and 6), or ``hip_ops.ACT_NONE`` (0: anything
+    else -- a Hardtanh with other bounds and a ``clamp`` call included -- stays an ordinary node)."""
     if node.op == "call_module":
-        return isinstance(mods[node.target], nn.ReLU)
-    if node.op == "call_function":
-        return node.target in (F.relu, torch.relu, torch.relu_)
-    if node.op == "call_method":
-        return node.target in ("relu", "relu_")
-    return False
+        m = mods[node.target]
+        if isinstance(m, nn.ReLU):
+            return hip_ops.ACT_RELU
+        if isinstance(m, nn.Hardtanh) and _is_const(m.min_val, 0) and _is_const(m.max_val, 6):      # nn.ReLU6 is one
+            return hip_ops.ACT_RELU6
+    elif node.op == "call_function":
+        if node.target in (F.relu, torch.relu, torch.relu_):
+            return hip_ops.ACT_RELU
+        if node.target is F.relu6:
+            return hip_ops.ACT_RELU6
+        if node.target in (F.hardtanh, F.hardtanh_):
+            lo, hi = _hardtanh_bounds(node)
+            if _is_const(lo, 0) and _is_const(hi, 6):
+                return hip_ops.ACT_RELU6
+    elif node.op == "call_method" and node.target in ("relu", "relu_"):
+        return hip_ops.ACT_RELU
+    return hip_ops.ACT_NONE
+
+
+def _act_arg(relu: Optional[torch.fx.Node], mods):
+    """The ``relu`` operand a fused call carries for the chain's activation node: ``False`` without one, ``True`` for a ReLU (as
+    ever), ``hip_ops.ACT_RELU6`` for a ReLU6."""
+    if relu is None:
+        return False
+    code = int(_is_relu(relu, mods))
+    return True if code == hip_ops.ACT_RELU else code
 
 
 def _is_add(node: torch.fx.Node) -> bool:
@@ -493,7 +529,7 @@ def _conv_stats_pairs(graph: torch.fx.Graph, op: Callable, pool_op: Optional[Cal
 
 
 def bn_chain(node: torch.fx.Node, mods, bare_add: bool, claimed: Optional[set] = None):
-    """``(add, relu, residual)`` of the chain ``node -> [+ other] -> [ReLU]`` behind BatchNorm call ``node`` whose links have no
+    """``(add, relu, residual)`` of the chain ``node -> [+ other] -> [ReLU / ReLU6]`` behind BatchNorm call ``node`` whose links have no
     other consumer (None where absent); ``x + x`` is no residual add.  ``bare_add``: an add that no sole ReLU follows is taken too
     (else the BatchNorm stands alone).  ``claimed``: the adds taken so far -- none is taken twice, the one taken here joins them."""
     users = list(node.users)
@@ -543,9 +579,9 @@ def _fold_chains(graph: torch.fx.Graph, mods, op: Callable, pool_op: Optional[Ca
                 s = graph.create_node("get_attr", "_pleas_scale_%s" % tag, (), {}, name="bn_scale")
                 t = graph.create_node("get_attr", "_pleas_shift_%s" % tag, (), {}, name="bn_shift")
             if window is not None:
-                fused = graph.create_node("call_function", pool_op, (node.args[0], s, t) + window + (True,), {}, name="bn_act_pool")
+                fused = graph.create_node("call_function", pool_op, (node.args[0], s, t) + window + (_act_arg(relu, mods),), {}, name="bn_act_pool")
             else:
-                fused = graph.create_node("call_function", op, (node.args[0], s, t, res, relu is not None), {}, name="bn_act")
+                fused = graph.create_node("call_function", op, (node.args[0], s, t, res, _act_arg(relu, mods)), {}, name="bn_act")
         last.replace_all_uses_with(fused)
         for dead in reversed(chain):
             graph.erase_node(dead)
@@ -595,7 +631,7 @@ def fuse_bn_act(model: nn.Module, op: Callable = _bn_act, train_stats: bool = Fa
                 inference: bool = False, train_convs: bool = False) -> Optional[torch.fx.GraphModule]:
     """fx copy of ``model`` (sharing its submodules) with every eval-mode BatchNorm2d chain replaced by
     ``op(x, scale, shift, residual_or_None, relu)`` -- the HIP kernel ``hip_ops.bn_act`` unless a test
-    passes its own.  Returns None when the model cannot be traced or holds nothing to fold; the caller
+    passes its own; ``relu`` is ``False``, ``True`` (a ReLU) or ``hip_ops.ACT_RELU6``.  Returns None when the model cannot be traced or holds nothing to fold; the caller
     then runs the model as it is (vendor kernels).
 
     ``train_stats=True``: BatchNorm2d modules that normalise with the BATCH's statistics (train mode -- the BN-reset pass

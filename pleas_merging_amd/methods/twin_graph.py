@@ -4,7 +4,7 @@
 layouts: *interleaved* (the reference's, :49-100: the two copies of a node side by side, the tracked call right behind
 them) and *split* (model2's whole chain on a second HIP stream, then model1's, a join, then every tracked call).  Both
 lower a node the same way (``_lower``) and track the same table (``_tracked_axes``); the split layout can also emit a
-``BatchNorm2d -> [+ other] -> [ReLU]`` chain as one ``pleas_bn_act_tracked`` launch (``_emit_chain``).
+``BatchNorm2d -> [+ other] -> [ReLU / ReLU6]`` chain as one ``pleas_bn_act_tracked`` launch (``_emit_chain``).
 tests/golden/graph_pins.json pins the node lists of every configuration.
 """
 from __future__ import annotations
@@ -20,7 +20,7 @@ from torch import nn
 from ..core.utils import Axis
 from .. import hip_ops
 from .source_forward import (BatchesPerForward, HipConv, _foldable, _foldable_train, _train_fold, bn_chain, fold_bn,
-                             own_conv_ok, own_dwconv_ok)
+                             _act_arg, _is_relu, own_conv_ok, own_dwconv_ok)
 
 
 def _node(graph: torch.fx.Graph, op: str, target, args=(), name: str = "n") -> torch.fx.Node:
@@ -75,17 +75,30 @@ class _SideStream:
 
 
 # ------------------------------------------------------------------------------------------ one node of one side
+def _relu6_in_place(node: torch.fx.Node) -> bool:
+    """Does this functional ReLU6 call overwrite its input?  ``F.hardtanh_(x, 0, 6)`` always; ``F.relu6(x, inplace)`` and
+    ``F.hardtanh(x, 0, 6, inplace)`` by their ``inplace`` argument, keyword or positional."""
+    if node.target is F.hardtanh_:
+        return True
+    at = 1 if node.target is F.relu6 else 3      # where ``inplace`` stands among the positional arguments
+    return bool(node.kwargs.get("inplace") or (len(node.args) > at and node.args[at]))
+
+
 def _out_of_place(twin: torch.fx.Graph, node: torch.fx.Node, lookup: Callable, submods) -> Optional[torch.fx.Node]:
     """Out-of-place twin of an in-place op (same values, new tensor), or None when ``node`` is not one.
     Deferred sinks read tracked activations after the forward, so nothing may overwrite them."""
     if node.op == "call_module" and isinstance(submods[node.target], nn.ReLU) and submods[node.target].inplace:
         return twin.call_function(torch.relu, (lookup(node.args[0]),))
+    if node.op == "call_module" and getattr(submods[node.target], "inplace", False) and _is_relu(node, submods) == hip_ops.ACT_RELU6:
+        return twin.call_function(F.relu6, (lookup(node.args[0]),))      # nn.ReLU6 / nn.Hardtanh(0, 6) with inplace=True
     if node.op == "call_function":
         if node.target is operator.iadd:
             return twin.call_function(operator.add, tuple(torch.fx.node.map_arg(node.args, lookup)))
         if node.target is torch.relu_ or (node.target is F.relu and (node.kwargs.get("inplace") or
                                                                     (len(node.args) > 1 and node.args[1]))):
             return twin.call_function(torch.relu, (lookup(node.args[0]),))
+        if _is_relu(node, submods) == hip_ops.ACT_RELU6 and _relu6_in_place(node):
+            return twin.call_function(F.relu6, (lookup(node.args[0]),))
     if node.op == "call_method" and node.target in ("relu_", "add_") and not node.kwargs:
         return twin.call_method(node.target[:-1], tuple(torch.fx.node.map_arg(node.args, lookup)))
     return None
@@ -168,8 +181,8 @@ def _derivable(chains: dict, absorbed: set, want: Dict[str, List[int]]) -> set:
 
 
 def _emit_chain(twin: torch.fx.Graph, root: nn.Module, chain, side: int, mod: nn.BatchNorm2d, env: dict,
-                state: Optional[BatchesPerForward], write_bn: bool) -> Tuple[torch.fx.Node, torch.fx.Node]:
-    """``BatchNorm -> [+ residual] -> [ReLU]`` whose links feed nothing else: ONE launch produces every node of the chain
+                state: Optional[BatchesPerForward], write_bn: bool, submods) -> Tuple[torch.fx.Node, torch.fx.Node]:
+    """``BatchNorm -> [+ residual] -> [ReLU / ReLU6]`` whose links feed nothing else: ONE launch produces every node of the chain
     (activation matching measures all of them), reading x and the residual once.  Enters the chain's members into
     ``env`` and returns the ``(scale, shift)`` nodes of the BatchNorm's affine map."""
     bn, add, relu, res = chain
@@ -184,7 +197,7 @@ def _emit_chain(twin: torch.fx.Graph, root: nn.Module, chain, side: int, mod: nn
         attrs = (_node(twin, "call_function", operator.getitem, (fold, 0), "bn_scale"),
                  _node(twin, "call_function", operator.getitem, (fold, 1), "bn_shift"))
     fused = _node(twin, "call_function", hip_ops.bn_act_tracked,
-                  (x, attrs[0], attrs[1], env[res] if res is not None else None, relu is not None, write_bn), "bn_chain")
+                  (x, attrs[0], attrs[1], env[res] if res is not None else None, _act_arg(relu, submods), write_bn), "bn_chain")
     for slot, member in enumerate((bn, add, relu)):
         if member is not None:
             env[member] = _node(twin, "call_function", operator.getitem, (fused, slot), "chain_out")
@@ -251,7 +264,7 @@ def _build_split_twin(model1: nn.Module, model2: nn.Module, axes: Iterable[Axis]
             if node in chains:
                 bn = chains[node][0]
                 folds[side][bn] = _emit_chain(twin, root, chains[node], side, model.get_submodule(bn.target), env[side],
-                                              state, bn not in derivable)
+                                              state, bn not in derivable, submods)
             elif node.op not in ("placeholder", "output") and node not in absorbed:
                 _lower(twin, node, side, model, env[side], submods, True)
         if side == 1:
